@@ -30,6 +30,16 @@ is one of the ranks.
 
 FLOPs are algorithmic: fwd = 4 B H S^2 D (/2 causal), bwd = 2.5 fwd.
 
+A plain run does only what the headline figure needs: it sets the workload up, warms up, times
+the --steps steps, writes the last step's outputs when --dump-outputs is given, and prints the
+result line (metric, value, unit, ms_per_step, the workload).  `--dump-outputs DIR` writes what
+the last timed step returned to its caller -- `out`, and with a backward `dq`, `dk`, `dv` (and
+`dbias` with --bias-grad) -- as DIR/<name>.npy in float32: the whole array up to 2^20 elements, a
+fixed seeded sample of 2^20 elements (flat indices, ascending) of a larger one; with several GPUs,
+rank 0's shard.  The inputs are seeded, so two builds run with the same arguments can be compared
+output for output.
+
+Everything below is measured only with `--full`.
 Besides the step time, every launch of the path -- the forward, and the backward's kernels
 (fa2_bwd_stages) -- is timed with HIP events on the stream it runs on.  `roofline` is the
 dominant (longest) kernel, `roofline_fwd` the north-star forward kernel, `roofline_dq` the dQ
@@ -41,7 +51,7 @@ the CPU oracle (oracle/reference.py, fp32, torch CPU threads) on a bounded slice
 workload, after the timed region, for `cpu_baseline`.
 
 Usage: python bench.py [--config cfg2|cfg3|cfg5] [--gpus N] [--steps K] [--warmup W] [--strong]
-                       [--bias] [--dropout P] [--no-cpu-baseline]
+                       [--bias] [--dropout P] [--dump-outputs DIR] [--full [--no-cpu-baseline]]
        torchrun --nproc-per-node N bench.py --gpus N ...
        python bench.py --gpus 2 --dry-run      (CPU/gloo: sharding + timing plumbing only)
 """
@@ -84,6 +94,8 @@ CONFIGS = {
 }
 DTYPES = {"bf16": torch.bfloat16, "fp16": torch.float16}
 DROPOUT_SEED = 20241008
+DUMP_SAMPLE = 1 << 20  # elements of one dumped array (4 MiB in float32; five arrays at the most)
+DUMP_SEED = 20251019
 
 
 def attn_flops(b, h, sq, sk, d, causal):
@@ -191,6 +203,22 @@ def launch_ranks(n: int, argv, timeout_s: float = 1800.0) -> int:
             time.sleep(0.1)
     finally:
         signal.signal(signal.SIGTERM, old)
+
+
+def dump_outputs(directory: str, arrays: dict) -> None:
+    """Write each tensor as directory/<name>.npy in float32: whole when it has at most DUMP_SAMPLE
+    elements, else its elements at DUMP_SAMPLE flat indices drawn with DUMP_SEED and sorted (the
+    same indices for every array of the same size, and from run to run)."""
+    import numpy as np
+
+    os.makedirs(directory, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_SAMPLE:
+            g = torch.Generator().manual_seed(DUMP_SEED)
+            idx = torch.randint(t.numel(), (DUMP_SAMPLE,), generator=g).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        np.save(os.path.join(directory, name + ".npy"), t.float().cpu().numpy())
 
 
 def cpu_info() -> dict:
@@ -341,11 +369,17 @@ def main():
     ap.add_argument("--bias-grad", action="store_true",
                     help="--bias that requires grad: the backward also computes dBias (library extension)")
     ap.add_argument("--dropout", type=float, default=0.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32, sampled when large)")
+    ap.add_argument("--full", action="store_true",
+                    help="also time every launch on its own (kernels, rooflines) and the CPU oracle (cpu_baseline)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle")
     ap.add_argument("--dry-run", action="store_true", help="CPU/gloo: sharding + timing plumbing, no kernels")
     ap.add_argument("--launch-timeout", type=float, default=1800.0, help="seconds before a self-launch gives up")
     args = ap.parse_args()
     preset = resolve(args)
+    if args.steps < 1:
+        raise SystemExit(f"--steps {args.steps}: at least one timed step")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:], args.launch_timeout))
@@ -399,9 +433,6 @@ def main():
 
     torch.cuda.set_device(device)
     from fa2_triton_amd import flash_attn_func
-    from fa2_triton_amd.backward import _flash_attn_backward
-    from fa2_triton_amd.utils import dropout_mask_words
-    from fa2_triton_amd.forward import _flash_attn_forward
 
     dtype = DTYPES[args.dtype]
     # this rank's rows of the synthetic global batch (seeded per shard start)
@@ -420,12 +451,13 @@ def main():
     seed = DROPOUT_SEED if p_drop > 0 else None
 
     def step():
+        """One step of the path; returns what its caller receives, by name."""
         if fwd_only:
             with torch.no_grad():
-                flash_attn_func(q, k, v, None, bias, p_drop, causal, None, seed)
-        else:
-            out = flash_attn_func(q, k, v, None, bias, p_drop, causal, None, seed)
-            torch.autograd.grad(out, grad_inputs, do)
+                return {"out": flash_attn_func(q, k, v, None, bias, p_drop, causal, None, seed)}
+        out = flash_attn_func(q, k, v, None, bias, p_drop, causal, None, seed)
+        grads = torch.autograd.grad(out, grad_inputs, do)
+        return dict(zip(("out", "dq", "dk", "dv", "dbias"), (out,) + tuple(grads)))
 
     for _ in range(args.warmup):
         step()
@@ -434,8 +466,9 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for _ in range(args.steps - 1):
         step()
+    outputs = step()  # the last timed step's results are kept for --dump-outputs
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     if dist:
@@ -443,6 +476,61 @@ def main():
     per_rank = gather_elapsed(elapsed, dist, world)
     elapsed = reduce_elapsed(elapsed, dist)
     value, ms_per_step = job_throughput(f_fwd_total, args.steps, elapsed, mult)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, outputs)
+    del outputs
+
+    workload = (f"B={b} Hq={h} Hkv={hkv} S={s} D={d} {args.dtype} {'causal' if causal else 'non-causal'} "
+                f"{'fwd only' if fwd_only else 'fwd+bwd'} per GPU ({preset['ref']})")
+    extras = []
+    if bias is not None:
+        extras.append("bias [1,1,S,S]")
+    if p_drop:
+        extras.append(f"dropout {p_drop}")
+    if extras:
+        workload += " + " + ", ".join(extras)
+    line = {
+        "metric": METRIC,
+        "value": round(value, 2),
+        "unit": "TFLOP/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 3),
+        "higher_is_better": True,
+        "scaling": scaling,
+        "vs_baseline": None,
+        "dtype": args.dtype,
+        "data": "synthetic N(0,0.5) Q/K/V, N(0,1) dO, resident in HBM",
+        "config": {
+            "workload": workload,
+            "config": args.config,
+            "global_batch": global_batch,
+            "per_gpu_batch": b,
+            "seq_len": s,
+            "heads": h,
+            "heads_kv": hkv,
+            "head_dim": d,
+            "causal": causal,
+            "fwd_only": fwd_only,
+            "bias": bias is not None,
+            "dropout_p": p_drop,
+            "parallelism": f"batch-sharded x{world} ({scaling} scaling), independent per-GPU launches, "
+                           "no data-path collectives (host gloo barrier + timer reduction only)",
+        },
+        "rank_elapsed_s": [round(t, 6) for t in per_rank],
+        "pct_of_peak_step": round(100 * value / world / PEAK_TFLOPS, 2),
+    }
+    if not args.full:  # the plain run ends here: the headline figure and nothing else
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if dist:
+            dist.destroy_process_group()
+        return
+
+    from fa2_triton_amd.backward import _flash_attn_backward
+    from fa2_triton_amd.forward import _flash_attn_forward
+    from fa2_triton_amd.utils import dropout_mask_words
 
     # ---- per-launch timing with HIP events on the launch stream ---------------------------
     # fwd: one launch; bwd: dQ (recomputes S, dP; also writes delta), then dK/dV, each timed
@@ -563,57 +651,18 @@ def main():
     if rank != 0:
         dist.destroy_process_group()
         return
-    workload = (f"B={b} Hq={h} Hkv={hkv} S={s} D={d} {args.dtype} {'causal' if causal else 'non-causal'} "
-                f"{'fwd only' if fwd_only else 'fwd+bwd'} per GPU ({preset['ref']})")
-    extras = []
-    if bias is not None:
-        extras.append("bias [1,1,S,S]")
-    if p_drop:
-        extras.append(f"dropout {p_drop}")
-    if extras:
-        workload += " + " + ", ".join(extras)
-    line = {
-        "metric": METRIC,
-        "value": round(value, 2),
-        "unit": "TFLOP/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(ms_per_step, 3),
-        "higher_is_better": True,
-        "scaling": scaling,
-        "vs_baseline": None,
-        "dtype": args.dtype,
-        "data": "synthetic N(0,0.5) Q/K/V, N(0,1) dO, resident in HBM",
-        "config": {
-            "workload": workload,
-            "config": args.config,
-            "global_batch": global_batch,
-            "per_gpu_batch": b,
-            "seq_len": s,
-            "heads": h,
-            "heads_kv": hkv,
-            "head_dim": d,
-            "causal": causal,
-            "fwd_only": fwd_only,
-            "bias": bias is not None,
-            "dropout_p": p_drop,
-            "parallelism": f"batch-sharded x{world} ({scaling} scaling), independent per-GPU launches, "
-                           "no data-path collectives (host gloo barrier + timer reduction only)",
-        },
-        "rank_elapsed_s": [round(t, 6) for t in per_rank],
+    line.update({
         "fwd_tflops": round(fwd_tf, 2),
         "bwd_tflops": round(bwd_tf, 2) if bwd_tf else None,
         "fwd_ms": round(t_fwd * 1e3, 4),
         "bwd_ms": round(t_bwd * 1e3, 4) if t_bwd else None,
         "pct_of_peak_fwd": round(100 * fwd_tf / PEAK_TFLOPS, 2),
         "pct_of_peak_bwd": round(100 * bwd_tf / PEAK_TFLOPS, 2) if bwd_tf else None,
-        "pct_of_peak_step": round(100 * value / world / PEAK_TFLOPS, 2),
         "roofline": roofline(dominant),
         "roofline_fwd": roofline("fwd_kernel"),
         "kernels": kernels,
         "cpu_baseline": cpu,
-    }
+    })
     if not fwd_only:
         line["roofline_dq"] = roofline("dq_kernel")
     if p_drop > 0:

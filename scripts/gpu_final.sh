@@ -19,6 +19,6 @@ fi
 bash scripts/profile_round.sh $TAG || exit $?
 for leg in "" "--no-causal" "--dropout 0.1" "--bias" "--config cfg2" "--config refbench" "--config cfg5" "--bias-grad --steps 3 --warmup 1"; do
   f=$OUT/bench_$(echo "x$leg" | tr -d ' -.').json
-  timeout -k 10 400 python bench.py $leg > $f 2> $f.err || { tail -5 $f.err; exit 1; }
+  timeout -k 10 400 python bench.py --full $leg > $f 2> $f.err || { tail -5 $f.err; exit 1; }
   python -c "import json; d=json.load(open('$f')); print('$leg', d['value'], d.get('fwd_tflops'), d.get('bwd_tflops'), {k: v['ms'] for k, v in d.get('kernels', {}).items()}, d.get('roofline_valu', {}).get('frac'))"
 done
