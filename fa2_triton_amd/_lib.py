@@ -53,6 +53,9 @@ class FwdArgs(ctypes.Structure):
         ("dropout_p", ctypes.c_float),
         ("dropout_seed", ctypes.c_uint64),
         ("dropout_mask", ctypes.c_void_p),
+        ("local", ctypes.c_int32),
+        ("window_left", ctypes.c_int32),
+        ("window_right", ctypes.c_int32),
     ]
 
 
@@ -100,6 +103,9 @@ class BwdArgs(ctypes.Structure):
         ("dkv_workspace", ctypes.c_void_p),
         ("dkv_workspace_bytes", ctypes.c_int64),
         ("dropout_mask", ctypes.c_void_p),
+        ("local", ctypes.c_int32),
+        ("window_left", ctypes.c_int32),
+        ("window_right", ctypes.c_int32),
     ]
 
 
@@ -109,7 +115,7 @@ class Policy(ctypes.Structure):
     _fields_ = [("disable", ctypes.c_uint32), ("grid_cap", ctypes.c_int32)]
 
 
-ABI_VERSION = 9  # FA2_ABI_VERSION in include/fa2_amd.h
+ABI_VERSION = 10  # FA2_ABI_VERSION in include/fa2_amd.h
 
 EXPORTED_SYMBOLS = ("fa2_fwd", "fa2_fwd_ex", "fa2_bwd", "fa2_bwd_stages", "fa2_bwd_stages_ex",
                     "fa2_bwd_dkv_workspace_bytes", "fa2_dropout_mask_bytes", "fa2_cu_seqlens_from_mask",

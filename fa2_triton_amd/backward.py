@@ -20,7 +20,7 @@ from torch import Tensor
 
 from . import _lib
 from .utils import (bshd_strides, check_dropout_mask, cu_seqlens_from_mask, encode_dtype, handle_dropout,
-                    infer_bias_strides, launch_on)
+                    infer_bias_strides, launch_on, set_window)
 
 
 def _fill_args(args, q: Tensor, k: Tensor, v: Tensor, o: Tensor, dO: Tensor, causal: bool) -> None:
@@ -70,12 +70,15 @@ def _flash_attn_backward(
     _delta: Optional[Tensor] = None,
     bias_grad: bool = False,
     dropout_mask: Optional[Tensor] = None,
+    *,
+    window_size: Tuple[int, int] = (-1, -1),
 ):
     """Returns (dq, dk, dv) -- the reference's contract -- or (dq, dk, dv, dbias) with
     `bias_grad=True`: dbias = dL/d(bias) in bias's shape and dtype.  The library's bias-gradient
     kernel sums dS = P (dP - delta) over the bias's broadcast dims in a fixed order into a fp32
     buffer of the bias's shape (deterministic; no [B, Hq, Sq, Sk] intermediate).  The reference
-    has no bias gradient (/root/reference/src/wrapper.py:86 returns None)."""
+    has no bias gradient (/root/reference/src/wrapper.py:86 returns None).  Keyword-only
+    `window_size=(left, right)`: the forward's sliding window (fa2_bwd_args.local, ABI 10)."""
     if attention_mask is not None:
         assert bias is None, "Attention mask is not supported along with attention bias. Just use bias instead."
         assert q.size(1) == k.size(1), "Attention mask is not supported with seqlen_q != seqlen_k"
@@ -129,6 +132,7 @@ def _flash_attn_backward(
     if dropout_mask is not None and dropout_p > 0.0:  # the forward's keep bits, read instead of redrawn
         check_dropout_mask(dropout_mask, batch, nheads_q, seqlen_q, seqlen_k, q.device)
         args.dropout_mask = dropout_mask.data_ptr()
+    set_window(args, window_size)
     dkv_ws = alloc_dkv_workspace(args, q.device)
     if dkv_ws is not None:
         args.dkv_workspace, args.dkv_workspace_bytes = dkv_ws.data_ptr(), dkv_ws.numel()

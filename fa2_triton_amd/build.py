@@ -50,6 +50,21 @@ def generated_sources():
                     with open(path, "w") as f:
                         f.write(body)
                 srcs.append(path)
+    # the sliding-window kernels (local_kernel.h), in units of their own so that none above grows
+    for dname, flag in DTYPES.items():
+        for dt in TILES:
+            path = os.path.join(GEN, f"local_{dname}_d{dt}.hip")
+            body = (
+                '#include "../local_kernel.h"\n'
+                "namespace fa2 {\n"
+                f"template hipError_t launch_fwd_local<{flag}, {dt}>(const fa2_fwd_args&, bool, hipStream_t);\n"
+                f"template hipError_t launch_bwd_local<{flag}, {dt}>(const fa2_bwd_args&, bool, int, hipStream_t);\n"
+                "}\n"
+            )
+            if not os.path.exists(path) or open(path).read() != body:
+                with open(path, "w") as f:
+                    f.write(body)
+            srcs.append(path)
     return srcs
 
 

@@ -56,6 +56,29 @@ int check_common(int B, int Hq, int Hkv, int Sq, int Sk, int D, int dtype, int l
   return FA2_OK;
 }
 
+// The sliding window of a call (ABI 10) in normal form, on the library's own copy of the args:
+// causal forces right = 0; a window with no bound is no window; one that bounds only the right
+// side at 0 is the causal mask.  What stays local has left >= 0 or right > 0 (negative = no
+// bound); what does not launches exactly the kernels of the same call without a window.
+template <typename Args>
+void normalise_window(Args& n) {
+  if (n.local) {
+    const int left = n.window_left < 0 ? -1 : n.window_left;
+    const int right = n.causal ? 0 : (n.window_right < 0 ? -1 : n.window_right);
+    if (left < 0 && right < 0) {
+      n.local = 0;
+    } else if (left < 0 && right == 0) {
+      n.local = 0;
+      n.causal = 1;
+    } else {
+      n.local = 1;
+      n.window_left = left;
+      n.window_right = right;
+    }
+  }
+  if (!n.local) n.window_left = n.window_right = 0;
+}
+
 template <typename F4, typename F8, typename F12, typename F16>
 hipError_t dispatch_dt(int dt, F4 f32, F8 f64, F12 f128, F16 f256) {
   switch (dt) {
@@ -109,6 +132,12 @@ int fa2_fwd_ex(const fa2_fwd_args* a, const fa2_policy* policy, void* stream) {
   if ((qs && (!a->q || !a->o || !a->lse)) || (ks && (!a->k || !a->v))) return fail(FA2_E_INVALID, "null tensor pointer");
   if (a->bias && a->bias_dtype != FA2_F16 && a->bias_dtype != FA2_BF16 && a->bias_dtype != FA2_F32)
     return fail(FA2_E_INVALID, "bias dtype %d", a->bias_dtype);
+  fa2_fwd_args norm = *a;
+  normalise_window(norm);
+  a = &norm;
+  if (a->local && (a->bias || a->dropout_p > 0.f))
+    return fail(FA2_E_UNSUPPORTED, "sliding window (left %d, right %d) with %s is not implemented", a->window_left,
+                a->window_right, a->bias ? "an attention bias" : "dropout");
   if (a->seqlen_q == 0) return FA2_OK;
   const int D = a->head_dim;
   const bool aligned = vec_ok(D, a->q, a->q_stride) && vec_ok(D, a->k, a->k_stride) &&
@@ -148,6 +177,12 @@ int fa2_bwd_stages_ex(const fa2_bwd_args* a, int stages, const fa2_policy* polic
   if (stages & ~15) return fail(FA2_E_INVALID, "stage mask %d", stages);
   if (a->dbias && !a->bias) return fail(FA2_E_INVALID, "dbias requested without a bias");
   if ((stages & 8) && !a->dbias) return fail(FA2_E_INVALID, "stage 8 (bias gradient) without a dbias buffer");
+  fa2_bwd_args norm = *a;
+  normalise_window(norm);
+  a = &norm;
+  if (a->local && (a->bias || a->dbias || a->dropout_p > 0.f))
+    return fail(FA2_E_UNSUPPORTED, "sliding window (left %d, right %d) with %s is not implemented", a->window_left,
+                a->window_right, a->dbias ? "a bias gradient" : (a->bias ? "an attention bias" : "dropout"));
   if (a->seqlen_q == 0 && a->seqlen_k == 0) return FA2_OK;  // empty dQ, dK, dV
   const int D = a->head_dim;
   bool aligned = vec_ok(D, a->q, a->q_stride) && vec_ok(D, a->k, a->k_stride) && vec_ok(D, a->v, a->v_stride) &&

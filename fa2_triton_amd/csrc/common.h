@@ -141,6 +141,11 @@ FA2_DEV float half_sum(float x) {
   return __uint_as_float(r[0]) + __uint_as_float(r[1]);
 }
 
+// One side of a sliding window (fa2_*_args.window_left / window_right) as a distance: a negative
+// bound means none, i.e. farther than any sequence is long, yet small enough that
+// row + diag +- bound stays inside an int.
+FA2_DEV int window_bound(int w) { return (w < 0 || w > (1 << 29)) ? (1 << 29) : w; }
+
 FA2_DEV f32x16 zero16() {
   f32x16 z;
 #pragma unroll

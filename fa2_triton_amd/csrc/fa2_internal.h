@@ -24,6 +24,15 @@ hipError_t launch_fwd_dt(const fa2_fwd_args& a, bool aligned, hipStream_t st);
 template <bool BF16, int DT>
 hipError_t launch_bwd_dt(const fa2_bwd_args& a, bool aligned, int stages, hipStream_t st);
 
+// Sliding-window (local) attention, ABI 10 (local_kernel.h): one translation unit of its own per
+// (dtype, head-dim tile).  Called by the two launchers above when a.local is set; api.hip has
+// normalised the window by then (causal folded into window_right = 0, a window that bounds
+// nothing or only restates the causal mask turned off) and rejected bias / dropout / dbias.
+template <bool BF16, int DT>
+hipError_t launch_fwd_local(const fa2_fwd_args& a, bool aligned, hipStream_t st);
+template <bool BF16, int DT>
+hipError_t launch_bwd_local(const fa2_bwd_args& a, bool aligned, int stages, hipStream_t st);
+
 hipError_t launch_cu_seqlens(const uint8_t* mask, int64_t stride, int batch, int seqlen,
                              int32_t* out, hipStream_t st);
 

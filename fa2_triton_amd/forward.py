@@ -7,6 +7,7 @@ call of the C ABI `fa2_fwd`; the varlen pack/unpack (:44-63, :118-120) disappear
 HIP kernel reads the padded tensors in place using device-side cu_seqlens.  Keyword-only
 `dropout_mask` (beyond the reference): an int32 buffer of dropout_mask_words(...) words that the
 forward fills with the keep bits it drew, for the backward to read instead of regenerating them.
+Keyword-only `window_size=(left, right)`: sliding-window attention (fa2_fwd_args.local, ABI 10).
 """
 import math
 from typing import Optional, Tuple
@@ -16,7 +17,7 @@ from torch import Tensor
 
 from . import _lib
 from .utils import (bshd_strides, check_dropout_mask, cu_seqlens_from_mask, encode_dtype, handle_dropout,
-                    infer_bias_strides, launch_on)
+                    infer_bias_strides, launch_on, set_window)
 
 
 def _flash_attn_forward(
@@ -31,6 +32,7 @@ def _flash_attn_forward(
     dropout_seed: Optional[int] = None,
     *,
     dropout_mask: Optional[Tensor] = None,
+    window_size: Tuple[int, int] = (-1, -1),
 ) -> Tuple[Tensor, Tensor, float, int]:
     if attention_mask is not None:
         assert bias is None, "Attention mask is not supported along with attention bias. Just use bias instead."
@@ -78,5 +80,6 @@ def _flash_attn_forward(
     if dropout_mask is not None and dropout_p > 0.0:
         check_dropout_mask(dropout_mask, batch, nheads_q, seqlen_q, seqlen_k, q.device)
         args.dropout_mask = dropout_mask.data_ptr()
+    set_window(args, window_size)
     _lib.check(launch_on(q, lambda st: _lib.fwd(args, st)))
     return o, lse, softmax_scale, dropout_seed

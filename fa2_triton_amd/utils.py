@@ -43,6 +43,25 @@ def infer_bias_strides(
     return stride_bb, stride_bh, bias.stride(2)
 
 
+def check_window_size(window_size) -> Tuple[int, int]:
+    """`window_size` as a pair of ints (left, right); anything else raises ValueError."""
+    ok = isinstance(window_size, (tuple, list)) and len(window_size) == 2 and all(
+        isinstance(w, int) and not isinstance(w, bool) for w in window_size)
+    if not ok:
+        raise ValueError(f"window_size must be a pair of ints (left, right), got {window_size!r}")
+    return int(window_size[0]), int(window_size[1])
+
+
+def set_window(args, window_size) -> None:
+    """The sliding window of fa2_fwd_args / fa2_bwd_args (ABI 10).  `local` is the switch: a
+    negative bound is stored as -1 (no bound on that side) and the library normalises the rest
+    (both unbounded: no window; causal: right = 0)."""
+    left, right = check_window_size(window_size)
+    left, right = min(max(left, -1), 2**30), min(max(right, -1), 2**30)  # (int32 fields)
+    args.local = int(left >= 0 or right >= 0)
+    args.window_left, args.window_right = (left, right) if args.local else (0, 0)
+
+
 def dropout_mask_words(batch: int, heads_q: int, seqlen_q: int, seqlen_k: int) -> int:
     """int32 words of a dropout keep mask (fa2_dropout_mask_bytes / 4 in include/fa2_amd.h):
     32 x 32 bit tiles, batch * heads_q * ceil(Sq / 32) * ceil(Sk / 32) * 32 words, plus one tile of

@@ -1,23 +1,26 @@
 """Public autograd op -- same surface as /root/reference/src/wrapper.py:10-100.
 
 `flash_attn_func(q, k, v, attention_mask=None, attention_bias=None, dropout_p=0.0,
-causal=False, softmax_scale=None, dropout_seed=None)` with q [B, Sq, Hq, D], k/v
-[B, Sk, Hkv, D] (fp16 / bf16), returns O [B, Sq, Hq, D].  Backward returns (dq, dk, dv) and
+causal=False, softmax_scale=None, dropout_seed=None, window_size=(-1, -1))` with q [B, Sq, Hq, D],
+k/v [B, Sk, Hkv, D] (fp16 / bf16), returns O [B, Sq, Hq, D].  Backward returns (dq, dk, dv) and
 no gradient for the mask and scalars, exactly as the reference (:62-86).  Beyond the
 reference (which returns None for the bias, :86): when `attention_bias` requires grad, its
 gradient dL/d(bias) is returned too.  With dropout the keep
-bits drawn by the forward are kept for the backward (see _keep_mask_buffer).
+bits drawn by the forward are kept for the backward (see _keep_mask_buffer).  Also beyond the
+reference: `window_size=(left, right)`, sliding-window (local) attention -- query i sees the keys
+i + (Lk - Lq) - left .. i + (Lk - Lq) + right of its sequence (a negative bound is no bound,
+`causal=True` forces right = 0), in O(S * window) work; not together with a bias or dropout.
 """
 import logging
 import os
-from typing import Optional
+from typing import Optional, Tuple
 
 import torch
 from torch import Tensor
 
 from .backward import _flash_attn_backward
 from .forward import _flash_attn_forward
-from .utils import dropout_mask_words
+from .utils import check_window_size, dropout_mask_words
 
 
 def _keep_mask_buffer(q: Tensor, k: Tensor, v: Tensor, dropout_p: float) -> Optional[Tensor]:
@@ -52,6 +55,7 @@ class FlashAttnFunc(torch.autograd.Function):
         causal: bool = False,
         softmax_scale: Optional[float] = None,
         dropout_seed: Optional[int] = None,
+        window_size: Tuple[int, int] = (-1, -1),
     ):
         # only the last dimension has to be contiguous (reference :41-43); bias fully (:44)
         q = q if q.stride(-1) == 1 else q.contiguous()
@@ -70,10 +74,12 @@ class FlashAttnFunc(torch.autograd.Function):
             softmax_scale=softmax_scale,
             dropout_seed=dropout_seed,
             dropout_mask=ctx.dropout_mask,
+            window_size=window_size,
         )
         ctx.save_for_backward(q, k, v, attention_bias, attention_mask, o, lse)
         ctx.causal = causal
         ctx.dropout_p = dropout_p
+        ctx.window_size = window_size
         return o
 
     @staticmethod
@@ -95,9 +101,10 @@ class FlashAttnFunc(torch.autograd.Function):
             dropout_seed=ctx.dropout_seed,
             bias_grad=bias_grad,
             dropout_mask=ctx.dropout_mask,
+            window_size=ctx.window_size,
         )
         dbias = grads[3] if bias_grad else None
-        return grads[0], grads[1], grads[2], None, dbias, None, None, None, None
+        return grads[0], grads[1], grads[2], None, dbias, None, None, None, None, None
 
 
 def flash_attn_func(
@@ -110,5 +117,7 @@ def flash_attn_func(
     causal: bool = False,
     softmax_scale: Optional[float] = None,
     dropout_seed: Optional[int] = None,
+    window_size: Tuple[int, int] = (-1, -1),
 ) -> Tensor:
-    return FlashAttnFunc.apply(q, k, v, attention_mask, attention_bias, dropout_p, causal, softmax_scale, dropout_seed)
+    return FlashAttnFunc.apply(q, k, v, attention_mask, attention_bias, dropout_p, causal, softmax_scale, dropout_seed,
+                               check_window_size(window_size))

@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define FA2_ABI_VERSION 9
+#define FA2_ABI_VERSION 10
 
 /* dtype codes: same numbers as the reference's encode_dtype (src/utils.py:102-109). */
 enum fa2_dtype { FA2_F16 = 16, FA2_BF16 = 17, FA2_F32 = 32 };
@@ -79,6 +79,15 @@ typedef struct fa2_fwd_args {
    * Philox launch) and then reads them (the D = 128 hand-placed forward runs with dropout only
    * then); O equals the no-buffer forward's within rounding, not bitwise. */
   uint32_t* dropout_mask;
+  /* sliding-window (local) attention (ABI 10).  local == 0: no window, the two fields below are
+   * ignored (a zero-initialised struct means what it meant before).  local != 0: with
+   * diag = Lk - Lq over the valid lengths (cu_seqlens under varlen), key j is visible to query i
+   * iff j < Lk and i + diag - window_left <= j <= i + diag + window_right; a negative bound means
+   * no bound on that side, and causal != 0 forces window_right = 0.  Rows with no visible key give
+   * O = 0 and LSE2 = -inf.  A window that bounds nothing (both negative) or only restates the
+   * causal mask (left < 0, right == 0) runs the kernels of the call without a window.  Not
+   * implemented together with a bias or dropout_p > 0: FA2_E_UNSUPPORTED. */
+  int32_t local, window_left, window_right;
 } fa2_fwd_args;
 
 /* Backward: dQ, dK, dV of the forward above.  dK/dV are written with heads_kv heads: the GQA
@@ -143,6 +152,11 @@ typedef struct fa2_bwd_args {
    * ever gates a (row, key) pair whose probability is 0, so its contents never reach a result and
    * the buffer needs no initialisation. */
   const uint32_t* dropout_mask;
+  /* sliding window (ABI 10), as in fa2_fwd_args and equal to the forward's.  Rows with no visible
+   * key get dQ = 0 and add nothing to dK / dV.  Not implemented together with a bias, a dbias
+   * buffer or dropout_p > 0: FA2_E_UNSUPPORTED.  The windowed dK/dV sums each GQA group in one
+   * workgroup: a dkv_workspace is accepted and left unused. */
+  int32_t local, window_left, window_right;
 } fa2_bwd_args;
 
 int fa2_fwd(const fa2_fwd_args* args, void* stream);
