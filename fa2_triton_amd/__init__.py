@@ -5,7 +5,9 @@ Drop-in for the operator of remi-or/fa2_triton (/root/reference/src/__init__.py:
 Triton kernels are replaced by hand-written HIP kernels in libfa2_amd.so (C ABI:
 include/fa2_amd.h).  The reference's pure-PyTorch oracle `flash_attn_reference` is test
 infrastructure here and lives in `oracle/` (it is not part of the shipped operator).
+Beyond the reference: `flash_attn_with_kvcache`, inference-only decode attention over a KV cache.
 """
+from .kvcache import flash_attn_with_kvcache
 from .wrapper import FlashAttnFunc, flash_attn_func
 
-__all__ = ["flash_attn_func", "FlashAttnFunc"]
+__all__ = ["flash_attn_func", "FlashAttnFunc", "flash_attn_with_kvcache"]

@@ -115,11 +115,50 @@ class Policy(ctypes.Structure):
     _fields_ = [("disable", ctypes.c_uint32), ("grid_cap", ctypes.c_int32)]
 
 
+class KvCacheArgs(ctypes.Structure):
+    """Mirror of fa2_kvcache_args (include/fa2_amd.h, ABI 10 minor 1)."""
+
+    _fields_ = [
+        ("q", ctypes.c_void_p),
+        ("k_cache", ctypes.c_void_p),
+        ("v_cache", ctypes.c_void_p),
+        ("o", ctypes.c_void_p),
+        ("lse", ctypes.c_void_p),
+        ("k_new", ctypes.c_void_p),
+        ("v_new", ctypes.c_void_p),
+        ("cache_seqlens", ctypes.c_void_p),
+        ("workspace", ctypes.c_void_p),
+        ("workspace_bytes", ctypes.c_int64),
+        ("q_stride", _i64x3),
+        ("k_cache_stride", _i64x3),
+        ("v_cache_stride", _i64x3),
+        ("o_stride", _i64x3),
+        ("k_new_stride", _i64x3),
+        ("v_new_stride", _i64x3),
+        ("batch", ctypes.c_int32),
+        ("heads_q", ctypes.c_int32),
+        ("heads_kv", ctypes.c_int32),
+        ("seqlen_q", ctypes.c_int32),
+        ("capacity", ctypes.c_int32),
+        ("head_dim", ctypes.c_int32),
+        ("seqlen_new", ctypes.c_int32),
+        ("causal", ctypes.c_int32),
+        ("window_left", ctypes.c_int32),
+        ("window_right", ctypes.c_int32),
+        ("dtype", ctypes.c_int32),
+        ("num_splits", ctypes.c_int32),
+        ("softmax_scale", ctypes.c_float),
+    ]
+
+
 ABI_VERSION = 10  # FA2_ABI_VERSION in include/fa2_amd.h
+ABI_MINOR = 1  # FA2_ABI_MINOR: additive revisions of ABI 10 (1: the fa2_kvcache_* entry points)
+KVCACHE_MIN_SPLIT_TILES, KVCACHE_MAX_SPLITS = 4, 128  # FA2_KVCACHE_* in include/fa2_amd.h
 
 EXPORTED_SYMBOLS = ("fa2_fwd", "fa2_fwd_ex", "fa2_bwd", "fa2_bwd_stages", "fa2_bwd_stages_ex",
                     "fa2_bwd_dkv_workspace_bytes", "fa2_dropout_mask_bytes", "fa2_cu_seqlens_from_mask",
-                    "fa2_last_error", "fa2_version")
+                    "fa2_last_error", "fa2_version", "fa2_abi_minor", "fa2_fwd_kvcache", "fa2_kvcache_num_splits",
+                    "fa2_kvcache_workspace_bytes")
 # fa2_path bits (fa2_policy.disable)
 PATH_FWD_HP, PATH_DQ_HP, PATH_DKDV_HP = 1, 2, 4
 
@@ -150,6 +189,15 @@ def bind(lib: ctypes.CDLL) -> ctypes.CDLL:
     lib.fa2_bwd_stages_ex.restype = ctypes.c_int
     lib.fa2_version.argtypes = []
     lib.fa2_version.restype = ctypes.c_int
+    if hasattr(lib, "fa2_abi_minor"):  # a library older than minor 1 is rejected by load()
+        lib.fa2_abi_minor.argtypes = []
+        lib.fa2_abi_minor.restype = ctypes.c_int
+        lib.fa2_fwd_kvcache.argtypes = [ctypes.POINTER(KvCacheArgs), ctypes.c_void_p]
+        lib.fa2_fwd_kvcache.restype = ctypes.c_int
+        lib.fa2_kvcache_num_splits.argtypes = [ctypes.POINTER(KvCacheArgs)]
+        lib.fa2_kvcache_num_splits.restype = ctypes.c_int
+        lib.fa2_kvcache_workspace_bytes.argtypes = [ctypes.POINTER(KvCacheArgs)]
+        lib.fa2_kvcache_workspace_bytes.restype = ctypes.c_int64
     return lib
 
 
@@ -170,6 +218,10 @@ def load() -> ctypes.CDLL:
         version = lib.fa2_version()
         if version != ABI_VERSION:
             raise RuntimeError(f"fa2_triton_amd: library ABI version {version}, expected {ABI_VERSION}")
+        minor = lib.fa2_abi_minor() if hasattr(lib, "fa2_abi_minor") else 0
+        if minor < ABI_MINOR:
+            raise RuntimeError(f"fa2_triton_amd: library {LIB_PATH} is ABI {version}.{minor}, this package needs "
+                               f"{ABI_VERSION}.{ABI_MINOR}; rebuild it with `python -m fa2_triton_amd.build`")
         _lib = lib
     return _lib
 

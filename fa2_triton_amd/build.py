@@ -65,6 +65,20 @@ def generated_sources():
                 with open(path, "w") as f:
                     f.write(body)
             srcs.append(path)
+    # the KV-cache decode kernel (kvcache_kernel.h), again in units of its own
+    for dname, flag in DTYPES.items():
+        for dt in TILES:
+            path = os.path.join(GEN, f"kvcache_{dname}_d{dt}.hip")
+            body = (
+                '#include "../kvcache_kernel.h"\n'
+                "namespace fa2 {\n"
+                f"template hipError_t launch_kvcache_split<{flag}, {dt}>(const fa2_kvcache_args&, int, hipStream_t);\n"
+                "}\n"
+            )
+            if not os.path.exists(path) or open(path).read() != body:
+                with open(path, "w") as f:
+                    f.write(body)
+            srcs.append(path)
     return srcs
 
 
@@ -131,7 +145,8 @@ def build(force: bool = False, jobs: int = 0) -> str:
     check_dev_env()
     os.makedirs(OBJ, exist_ok=True)
     generated_headers()
-    srcs = [os.path.join(CSRC, "api.hip"), os.path.join(CSRC, "misc.hip")] + generated_sources()
+    srcs = [os.path.join(CSRC, "api.hip"), os.path.join(CSRC, "misc.hip"),
+            os.path.join(CSRC, "kvcache.hip")] + generated_sources()
     dep_t = deps_mtime()
     jobs = jobs or min(16, os.cpu_count() or 4)
     with ThreadPoolExecutor(max_workers=jobs) as ex:

@@ -7,6 +7,7 @@
 #include <stdio.h>
 
 #include "fa2_internal.h"
+#include "kvcache_host.h"
 #if FA2_HP_STAMPS
 #include "common.h"
 #endif
@@ -77,6 +78,24 @@ void normalise_window(Args& n) {
     }
   }
   if (!n.local) n.window_left = n.window_right = 0;
+}
+
+// The sizes, dtype and split count of a KV-cache call: what fa2_kvcache_num_splits and
+// fa2_kvcache_workspace_bytes need to be meaningful, checked before anything else.
+int kvcache_check_sizes(const fa2_kvcache_args* a) {
+  if (a->batch < 1 || a->heads_q < 1 || a->heads_kv < 1 || a->seqlen_q < 1 || a->capacity < 1 || a->head_dim < 1 ||
+      a->seqlen_new < 0)
+    return fail(FA2_E_INVALID, "bad sizes B=%d Hq=%d Hkv=%d Sq=%d capacity=%d D=%d seqlen_new=%d", a->batch, a->heads_q,
+                a->heads_kv, a->seqlen_q, a->capacity, a->head_dim, a->seqlen_new);
+  if (a->heads_q % a->heads_kv != 0)
+    return fail(FA2_E_INVALID, "heads_q=%d is not divisible by heads_kv=%d", a->heads_q, a->heads_kv);
+  if (a->dtype != FA2_F16 && a->dtype != FA2_BF16) return fail(FA2_E_INVALID, "dtype %d: only fp16 and bf16", a->dtype);
+  if (!pick_dt(a->head_dim)) return fail(FA2_E_UNSUPPORTED, "head_dim %d > 256", a->head_dim);
+  if (a->capacity > (1 << 30) || a->seqlen_q > (1 << 24))
+    return fail(FA2_E_UNSUPPORTED, "capacity %d > 2^30 or seqlen_q %d > 2^24", a->capacity, a->seqlen_q);
+  if (a->num_splits < 0 || a->num_splits > FA2_KVCACHE_MAX_SPLITS)
+    return fail(FA2_E_INVALID, "num_splits=%d must be in 0 .. %d", a->num_splits, FA2_KVCACHE_MAX_SPLITS);
+  return FA2_OK;
 }
 
 template <typename F4, typename F8, typename F12, typename F16>
@@ -236,6 +255,61 @@ int fa2_cu_seqlens_from_mask(const uint8_t* mask, int64_t mask_row_stride, int32
   if (!mask || !cu_seqlens || batch < 1 || seqlen < 0) return fail(FA2_E_INVALID, "bad cu_seqlens arguments");
   return hip_status(fa2::launch_cu_seqlens(mask, mask_row_stride, batch, seqlen, cu_seqlens, (hipStream_t)stream),
                     "fa2_cu_seqlens_from_mask launch");
+}
+
+int fa2_abi_minor(void) { return FA2_ABI_MINOR; }
+
+int fa2_kvcache_num_splits(const fa2_kvcache_args* a) {
+  if (!a || kvcache_check_sizes(a)) return 1;
+  if (a->num_splits >= 1) return a->num_splits;
+  return fa2::kv_auto_splits(*a, fa2::kv_cu_count());
+}
+
+int64_t fa2_kvcache_workspace_bytes(const fa2_kvcache_args* a) {
+  if (!a || kvcache_check_sizes(a)) return 0;
+  return fa2::kv_workspace_bytes(*a, fa2_kvcache_num_splits(a));
+}
+
+int fa2_fwd_kvcache(const fa2_kvcache_args* a, void* stream) {
+  if (!a) return fail(FA2_E_INVALID, "null args");
+  if (int rc = kvcache_check_sizes(a)) return rc;
+  if (!a->q || !a->k_cache || !a->v_cache || !a->o) return fail(FA2_E_INVALID, "null tensor pointer");
+  if ((a->k_new != nullptr) != (a->v_new != nullptr)) return fail(FA2_E_INVALID, "k_new and v_new must be given together");
+  if (a->k_new ? a->seqlen_new < 1 : a->seqlen_new != 0)
+    return fail(FA2_E_INVALID, "seqlen_new=%d %s k_new / v_new", a->seqlen_new, a->k_new ? "with" : "without");
+  const int D = a->head_dim;
+  if (D % 8 != 0) return fail(FA2_E_UNSUPPORTED, "head_dim %d is not a multiple of 8 (16-byte rows)", D);
+  bool aligned = vec_ok(D, a->q, a->q_stride) && vec_ok(D, a->k_cache, a->k_cache_stride) &&
+                 vec_ok(D, a->v_cache, a->v_cache_stride) && vec_ok(D, a->o, a->o_stride);
+  if (a->k_new) aligned = aligned && vec_ok(D, a->k_new, a->k_new_stride) && vec_ok(D, a->v_new, a->v_new_stride);
+  if (!aligned) return fail(FA2_E_UNSUPPORTED, "a tensor's rows are not 16-byte aligned (pointer or strides)");
+  const int nsplit = fa2_kvcache_num_splits(a);
+  const int64_t need = fa2::kv_workspace_bytes(*a, nsplit);
+  if (need > 0) {
+    if (!a->workspace || a->workspace_bytes < need)
+      return fail(FA2_E_INVALID, "workspace_bytes %lld < %lld required for %d splits",
+                  (long long)(a->workspace ? a->workspace_bytes : 0), (long long)need, nsplit);
+    if (!aligned16(a->workspace)) return fail(FA2_E_INVALID, "workspace must be 16-byte aligned");
+  }
+  if (fa2::kv_units(*a) * nsplit > 0x7FFFFFFFll) return fail(FA2_E_UNSUPPORTED, "grid of %lld units x %d splits", (long long)fa2::kv_units(*a), nsplit);
+  hipStream_t st = (hipStream_t)stream;
+  if (a->k_new)
+    if (int rc = hip_status(fa2::launch_kvcache_append(*a, st), "fa2_fwd_kvcache append launch")) return rc;
+  const bool bf = a->dtype == FA2_BF16;
+  hipError_t e;
+  if (bf)
+    e = dispatch_dt(pick_dt(D), [&] { return fa2::launch_kvcache_split<true, 32>(*a, nsplit, st); },
+                    [&] { return fa2::launch_kvcache_split<true, 64>(*a, nsplit, st); },
+                    [&] { return fa2::launch_kvcache_split<true, 128>(*a, nsplit, st); },
+                    [&] { return fa2::launch_kvcache_split<true, 256>(*a, nsplit, st); });
+  else
+    e = dispatch_dt(pick_dt(D), [&] { return fa2::launch_kvcache_split<false, 32>(*a, nsplit, st); },
+                    [&] { return fa2::launch_kvcache_split<false, 64>(*a, nsplit, st); },
+                    [&] { return fa2::launch_kvcache_split<false, 128>(*a, nsplit, st); },
+                    [&] { return fa2::launch_kvcache_split<false, 256>(*a, nsplit, st); });
+  if (int rc = hip_status(e, "fa2_fwd_kvcache launch")) return rc;
+  if (nsplit > 1) return hip_status(fa2::launch_kvcache_combine(*a, nsplit, st), "fa2_fwd_kvcache combine launch");
+  return FA2_OK;
 }
 
 #if FA2_HP_STAMPS

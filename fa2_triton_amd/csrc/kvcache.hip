@@ -1,0 +1,85 @@
+// kvcache.hip -- the small kernels around kvcache_split_kernel (kvcache_kernel.h): the append of
+// new key / value rows to the cache and the combination of the key splits' partial results.
+#include "common.h"
+#include "fa2_internal.h"
+#include "kvcache_host.h"
+
+namespace fa2 {
+
+// One thread per 16-byte chunk of a new row: k_new[b, n, h] -> k_cache[b, L_b + n, h] (and V), with
+// L_b = cache_seqlens[b] clamped to [0, capacity] on the device.  A row whose position is at or
+// past the capacity is dropped, so whatever cache_seqlens holds, only rows [0, capacity) of the
+// batch's own cache are written.  (dtype-blind: 16-bit elements moved as raw bits.)
+__global__ void __launch_bounds__(256) kvcache_append_kernel(const fa2_kvcache_args p) {
+  const int chunks = p.head_dim >> 3;
+  const int64_t total = (int64_t)p.batch * p.seqlen_new * p.heads_kv * chunks;
+  int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= total) return;
+  const int c = (int)(idx % chunks);
+  idx /= chunks;
+  const int h = (int)(idx % p.heads_kv);
+  idx /= p.heads_kv;
+  const int n = (int)(idx % p.seqlen_new), b = (int)(idx / p.seqlen_new);
+  int L = p.cache_seqlens ? p.cache_seqlens[b] : p.capacity;
+  L = min(max(L, 0), p.capacity);
+  const int64_t pos = (int64_t)L + n;
+  if (pos >= p.capacity) return;
+  const uint16_t* ks = (const uint16_t*)p.k_new + b * p.k_new_stride[0] + n * p.k_new_stride[1] + h * p.k_new_stride[2] + 8 * c;
+  const uint16_t* vs = (const uint16_t*)p.v_new + b * p.v_new_stride[0] + n * p.v_new_stride[1] + h * p.v_new_stride[2] + 8 * c;
+  uint16_t* kd = (uint16_t*)p.k_cache + b * p.k_cache_stride[0] + pos * p.k_cache_stride[1] + h * p.k_cache_stride[2] + 8 * c;
+  uint16_t* vd = (uint16_t*)p.v_cache + b * p.v_cache_stride[0] + pos * p.v_cache_stride[1] + h * p.v_cache_stride[2] + 8 * c;
+  const u32x4 kv = *(const u32x4*)ks, vv = *(const u32x4*)vs;
+  *(u32x4*)kd = kv;
+  *(u32x4*)vd = vv;
+}
+
+// Per output row (b, h, i), 64 threads (4 columns each), 4 rows per workgroup:
+//   m = max_s lse_s,  w_s = 2^(lse_s - m),  O = sum_s w_s O_s / sum_s w_s,  LSE2 = m + log2 sum_s w_s
+// summed in split order.  A split with lse_s = -inf (no visible key) has weight 0 and its partial O
+// is not read into the sum; all -inf gives O = 0, LSE2 = -inf.
+template <bool BF16>
+__global__ void __launch_bounds__(256) kvcache_combine_kernel(const fa2_kvcache_args p, const int nsplit) {
+  using E = Elem<BF16>;
+  const int D = p.head_dim, Sq = p.seqlen_q, Hq = p.heads_q;
+  const int64_t nrow = (int64_t)p.batch * Hq * Sq;
+  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= nrow) return;
+  const int d0 = 4 * (threadIdx.x & 63);
+  const float* ws_o = (const float*)p.workspace;
+  const float* ws_l = ws_o + (int64_t)nsplit * nrow * D;
+  float m = kNegInf;
+  for (int s = 0; s < nsplit; ++s) m = fmaxf(m, ws_l[s * nrow + row]);
+  float sum = 0.f;
+  f32x4 o = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int s = 0; s < nsplit; ++s) {
+    const float l = ws_l[s * nrow + row];
+    const float w = l == kNegInf ? 0.f : __builtin_amdgcn_exp2f(l - m);
+    sum += w;
+    if (w > 0.f && d0 < D) o += *(const f32x4*)(ws_o + (s * nrow + row) * D + d0) * w;
+  }
+  const float inv = sum > 0.f ? 1.f / sum : 0.f;
+  o *= inv;
+  const int i = (int)(row % Sq), h = (int)((row / Sq) % Hq), b = (int)(row / ((int64_t)Sq * Hq));
+  if (d0 < D) {
+    uint16_t* orow = (uint16_t*)p.o + b * p.o_stride[0] + i * p.o_stride[1] + h * p.o_stride[2];
+    *(u32x2*)(orow + d0) = u32x2{E::pack2(o[0], o[1]), E::pack2(o[2], o[3])};
+  }
+  if ((threadIdx.x & 63) == 0 && p.lse) p.lse[row] = sum > 0.f ? m + __builtin_amdgcn_logf(sum) : kNegInf;
+}
+
+hipError_t launch_kvcache_append(const fa2_kvcache_args& a, hipStream_t st) {
+  const int64_t total = (int64_t)a.batch * a.seqlen_new * a.heads_kv * (a.head_dim >> 3);
+  if (total <= 0) return hipSuccess;
+  hipLaunchKernelGGL(kvcache_append_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_kvcache_combine(const fa2_kvcache_args& a, int nsplit, hipStream_t st) {
+  const int64_t nrow = (int64_t)a.batch * a.heads_q * a.seqlen_q;
+  const dim3 grid((unsigned)((nrow + 3) / 4));
+  if (a.dtype == FA2_BF16) hipLaunchKernelGGL((kvcache_combine_kernel<true>), grid, dim3(256), 0, st, a, nsplit);
+  else hipLaunchKernelGGL((kvcache_combine_kernel<false>), grid, dim3(256), 0, st, a, nsplit);
+  return hipGetLastError();
+}
+
+}  // namespace fa2

@@ -199,8 +199,70 @@ typedef struct fa2_policy {
 int fa2_fwd_ex(const fa2_fwd_args* args, const fa2_policy* policy, void* stream);
 int fa2_bwd_stages_ex(const fa2_bwd_args* args, int stages, const fa2_policy* policy, void* stream);
 
+/* KV-cache decode attention (ABI 10, minor 1): O = softmax(scale * Q K^T, masks) V for a few query
+ * tokens against a pre-allocated key / value cache whose sequences have their own filled lengths,
+ * read on the device (no host synchronisation; the call can be captured in a graph).  Forward
+ * only.  Not implemented: paged caches (block tables), rotary embedding, bias, dropout, backward.
+ *
+ *  - L_b, the valid keys of batch b: cache_seqlens[b] clamped to [0, capacity] (NULL: capacity);
+ *    with k_new / v_new, min(that + seqlen_new, capacity) after the new rows n = 0 .. seqlen_new - 1
+ *    were written to the cache rows cache_seqlens[b] + n (rows that would land at or past capacity
+ *    are not written; nothing outside [0, capacity) of a batch row is ever written).  cache_seqlens
+ *    itself is not modified.
+ *  - query i sees key j iff j < L_b and, with diag = L_b - seqlen_q (bottom-right aligned),
+ *    i + diag - window_left <= j <= i + diag + window_right; a negative bound means no bound on
+ *    that side and causal != 0 forces window_right = 0.  Rows with no visible key give O = 0 and
+ *    LSE2 = -inf.
+ *  - work is cut into (batch, kv head, 32-row tile of the group's heads_q / heads_kv x seqlen_q
+ *    rows, key split) units; with more than one split the units write fp32 partial results into
+ *    `workspace` and a second kernel combines them in split order (bitwise reproducible).
+ *  - every row of q, k_cache, v_cache, o, k_new, v_new must be 16-byte aligned (head_dim % 8 == 0,
+ *    aligned pointers, strides % 8 == 0), else FA2_E_UNSUPPORTED. */
+typedef struct fa2_kvcache_args {
+  const void* q;          /* [B, Sq, Hq, D] */
+  void* k_cache;          /* [B, capacity, Hkv, D]; written only when k_new is given */
+  void* v_cache;          /* [B, capacity, Hkv, D] */
+  void* o;                /* [B, Sq, Hq, D], same dtype as q; every element is written */
+  float* lse;             /* optional [B, Hq, Sq] contiguous fp32 LSE2, or NULL */
+  const void* k_new;      /* optional [B, seqlen_new, Hkv, D] rows to append first, or NULL */
+  const void* v_new;      /* given exactly when k_new is */
+  const int32_t* cache_seqlens; /* optional [B] device int32, or NULL (every sequence fills the cache) */
+  void* workspace;        /* fa2_kvcache_workspace_bytes(args) bytes, 16-byte aligned; scratch */
+  int64_t workspace_bytes;
+  int64_t q_stride[3];    /* batch, seq, head strides (elements) */
+  int64_t k_cache_stride[3];
+  int64_t v_cache_stride[3];
+  int64_t o_stride[3];
+  int64_t k_new_stride[3];
+  int64_t v_new_stride[3];
+  int32_t batch, heads_q, heads_kv, seqlen_q, capacity, head_dim;
+  int32_t seqlen_new;     /* 0 without k_new / v_new */
+  int32_t causal;
+  int32_t window_left, window_right; /* negative: no bound */
+  int32_t dtype;          /* FA2_F16 or FA2_BF16 (q, caches, new rows, o) */
+  int32_t num_splits;     /* 0: chosen by fa2_kvcache_num_splits; 1 .. 128: forced */
+  float softmax_scale;
+} fa2_kvcache_args;
+
+int fa2_fwd_kvcache(const fa2_kvcache_args* args, void* stream);
+/* The key splits the call will use: num_splits when forced, else the smallest count that gives
+ * about two workgroups per compute unit over the B * Hkv * ceil(Hq / Hkv * Sq / 32) units, never
+ * leaving a split fewer than FA2_KVCACHE_MIN_SPLIT_TILES 64-key tiles of the key span (capacity,
+ * or the window's span when window_left >= 0), at most 128.  A function of the shapes only (host
+ * arithmetic; 1 for arguments fa2_fwd_kvcache would reject). */
+#define FA2_KVCACHE_MIN_SPLIT_TILES 4
+#define FA2_KVCACHE_MAX_SPLITS 128
+int fa2_kvcache_num_splits(const fa2_kvcache_args* args);
+/* Bytes of workspace: 0 with one split, else nsplit * B * Hq * Sq * (D + 1) * 4 (the fp32 partial
+ * outputs [nsplit, B, Hq, Sq, D] followed by the partial LSE2 [nsplit, B, Hq, Sq]). */
+int64_t fa2_kvcache_workspace_bytes(const fa2_kvcache_args* args);
+
 const char* fa2_last_error(void);
 int fa2_version(void);
+/* Additive revisions of one ABI version (FA2_ABI_VERSION stays what callers compiled against):
+ * minor 1 added the fa2_kvcache_* entry points and this function. */
+#define FA2_ABI_MINOR 1
+int fa2_abi_minor(void);
 
 #ifdef __cplusplus
 }
