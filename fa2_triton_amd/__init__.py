@@ -7,7 +7,7 @@ include/fa2_amd.h).  The reference's pure-PyTorch oracle `flash_attn_reference` 
 infrastructure here and lives in `oracle/` (it is not part of the shipped operator).
 Beyond the reference: `flash_attn_with_kvcache`, inference-only decode attention over a KV cache.
 """
-from .kvcache import flash_attn_with_kvcache
+from .kvcache import flash_attn_with_kvcache, flash_attn_with_paged_kvcache
 from .wrapper import FlashAttnFunc, flash_attn_func
 
-__all__ = ["flash_attn_func", "FlashAttnFunc", "flash_attn_with_kvcache"]
+__all__ = ["flash_attn_func", "FlashAttnFunc", "flash_attn_with_kvcache", "flash_attn_with_paged_kvcache"]

@@ -79,6 +79,20 @@ def generated_sources():
                 with open(path, "w") as f:
                     f.write(body)
             srcs.append(path)
+    # its paged variant (kvcache_paged_kernel.h)
+    for dname, flag in DTYPES.items():
+        for dt in TILES:
+            path = os.path.join(GEN, f"kvcache_paged_{dname}_d{dt}.hip")
+            body = (
+                '#include "../kvcache_paged_kernel.h"\n'
+                "namespace fa2 {\n"
+                f"template hipError_t launch_kvcache_paged_split<{flag}, {dt}>(const fa2_paged_kvcache_args&, int, hipStream_t);\n"
+                "}\n"
+            )
+            if not os.path.exists(path) or open(path).read() != body:
+                with open(path, "w") as f:
+                    f.write(body)
+            srcs.append(path)
     return srcs
 
 

@@ -270,9 +270,10 @@ int64_t fa2_kvcache_workspace_bytes(const fa2_kvcache_args* a) {
   return fa2::kv_workspace_bytes(*a, fa2_kvcache_num_splits(a));
 }
 
-int fa2_fwd_kvcache(const fa2_kvcache_args* a, void* stream) {
-  if (!a) return fail(FA2_E_INVALID, "null args");
-  if (int rc = kvcache_check_sizes(a)) return rc;
+// Everything fa2_fwd_kvcache checks after the sizes, shared with the paged call (whose pools are
+// k_cache / v_cache with block, row and head strides): pointers, the new rows, 16-byte rows, the
+// workspace and the grid.  On success *nsplit_out is the split count of the call.
+static int kvcache_check_call(const fa2_kvcache_args* a, int* nsplit_out) {
   if (!a->q || !a->k_cache || !a->v_cache || !a->o) return fail(FA2_E_INVALID, "null tensor pointer");
   if ((a->k_new != nullptr) != (a->v_new != nullptr)) return fail(FA2_E_INVALID, "k_new and v_new must be given together");
   if (a->k_new ? a->seqlen_new < 1 : a->seqlen_new != 0)
@@ -292,6 +293,16 @@ int fa2_fwd_kvcache(const fa2_kvcache_args* a, void* stream) {
     if (!aligned16(a->workspace)) return fail(FA2_E_INVALID, "workspace must be 16-byte aligned");
   }
   if (fa2::kv_units(*a) * nsplit > 0x7FFFFFFFll) return fail(FA2_E_UNSUPPORTED, "grid of %lld units x %d splits", (long long)fa2::kv_units(*a), nsplit);
+  *nsplit_out = nsplit;
+  return FA2_OK;
+}
+
+int fa2_fwd_kvcache(const fa2_kvcache_args* a, void* stream) {
+  if (!a) return fail(FA2_E_INVALID, "null args");
+  if (int rc = kvcache_check_sizes(a)) return rc;
+  int nsplit = 1;
+  if (int rc = kvcache_check_call(a, &nsplit)) return rc;
+  const int D = a->head_dim;
   hipStream_t st = (hipStream_t)stream;
   if (a->k_new)
     if (int rc = hip_status(fa2::launch_kvcache_append(*a, st), "fa2_fwd_kvcache append launch")) return rc;
@@ -309,6 +320,60 @@ int fa2_fwd_kvcache(const fa2_kvcache_args* a, void* stream) {
                     [&] { return fa2::launch_kvcache_split<false, 256>(*a, nsplit, st); });
   if (int rc = hip_status(e, "fa2_fwd_kvcache launch")) return rc;
   if (nsplit > 1) return hip_status(fa2::launch_kvcache_combine(*a, nsplit, st), "fa2_fwd_kvcache combine launch");
+  return FA2_OK;
+}
+
+// The sizes of a paged call: kvcache_check_sizes on the base, then the page size and the table
+// geometry (max_blocks is capacity / page_block_size).
+static int paged_kvcache_check_sizes(const fa2_paged_kvcache_args* a) {
+  if (int rc = kvcache_check_sizes(&a->base)) return rc;
+  const int P = a->page_block_size;
+  if (P < 16 || (P & (P - 1)) != 0) return fail(FA2_E_INVALID, "page_block_size=%d must be a power of two >= 16", P);
+  if (a->num_blocks < 1) return fail(FA2_E_INVALID, "num_blocks=%d must be >= 1", a->num_blocks);
+  if (a->base.capacity % P != 0)
+    return fail(FA2_E_INVALID, "capacity=%d must be max_blocks * page_block_size (a multiple of %d)", a->base.capacity, P);
+  return FA2_OK;
+}
+
+int fa2_paged_kvcache_num_splits(const fa2_paged_kvcache_args* a) {
+  if (!a || paged_kvcache_check_sizes(a)) return 1;
+  return fa2_kvcache_num_splits(&a->base);
+}
+
+int64_t fa2_paged_kvcache_workspace_bytes(const fa2_paged_kvcache_args* a) {
+  if (!a || paged_kvcache_check_sizes(a)) return 0;
+  return fa2_kvcache_workspace_bytes(&a->base);
+}
+
+int fa2_fwd_kvcache_paged(const fa2_paged_kvcache_args* a, void* stream) {
+  if (!a) return fail(FA2_E_INVALID, "null args");
+  if (int rc = paged_kvcache_check_sizes(a)) return rc;
+  if (!a->block_table) return fail(FA2_E_INVALID, "null block_table");
+  const int64_t max_blocks = a->base.capacity / a->page_block_size;
+  if (a->block_table_stride < max_blocks)
+    return fail(FA2_E_INVALID, "block_table_stride %lld < max_blocks %lld (capacity / page_block_size)",
+                (long long)a->block_table_stride, (long long)max_blocks);
+  int nsplit = 1;
+  if (int rc = kvcache_check_call(&a->base, &nsplit)) return rc;
+  const int D = a->base.head_dim;
+  hipStream_t st = (hipStream_t)stream;
+  if (a->base.k_new)
+    if (int rc = hip_status(fa2::launch_kvcache_paged_append(*a, st), "fa2_fwd_kvcache_paged append launch")) return rc;
+  const bool bf = a->base.dtype == FA2_BF16;
+  hipError_t e;
+  if (bf)
+    e = dispatch_dt(pick_dt(D), [&] { return fa2::launch_kvcache_paged_split<true, 32>(*a, nsplit, st); },
+                    [&] { return fa2::launch_kvcache_paged_split<true, 64>(*a, nsplit, st); },
+                    [&] { return fa2::launch_kvcache_paged_split<true, 128>(*a, nsplit, st); },
+                    [&] { return fa2::launch_kvcache_paged_split<true, 256>(*a, nsplit, st); });
+  else
+    e = dispatch_dt(pick_dt(D), [&] { return fa2::launch_kvcache_paged_split<false, 32>(*a, nsplit, st); },
+                    [&] { return fa2::launch_kvcache_paged_split<false, 64>(*a, nsplit, st); },
+                    [&] { return fa2::launch_kvcache_paged_split<false, 128>(*a, nsplit, st); },
+                    [&] { return fa2::launch_kvcache_paged_split<false, 256>(*a, nsplit, st); });
+  if (int rc = hip_status(e, "fa2_fwd_kvcache_paged launch")) return rc;
+  if (nsplit > 1)
+    return hip_status(fa2::launch_kvcache_combine(a->base, nsplit, st), "fa2_fwd_kvcache_paged combine launch");
   return FA2_OK;
 }
 

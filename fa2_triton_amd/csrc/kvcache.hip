@@ -33,6 +33,38 @@ __global__ void __launch_bounds__(256) kvcache_append_kernel(const fa2_kvcache_a
   *(u32x4*)vd = vv;
 }
 
+// The same append into a paged cache: logical position pos = L_b + n of batch b is row pos % P of
+// block block_table[b, pos / P], the entry clamped into [0, num_blocks - 1].  Positions at or past
+// capacity = max_blocks * P are dropped, so only table entries [0, max_blocks) are read and only
+// blocks of the pool are written, whatever cache_seqlens and the table hold.
+__global__ void __launch_bounds__(256) kvcache_paged_append_kernel(const fa2_paged_kvcache_args pp) {
+  const fa2_kvcache_args& p = pp.base;
+  const int chunks = p.head_dim >> 3;
+  const int64_t total = (int64_t)p.batch * p.seqlen_new * p.heads_kv * chunks;
+  int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= total) return;
+  const int c = (int)(idx % chunks);
+  idx /= chunks;
+  const int h = (int)(idx % p.heads_kv);
+  idx /= p.heads_kv;
+  const int n = (int)(idx % p.seqlen_new), b = (int)(idx / p.seqlen_new);
+  int L = p.cache_seqlens ? p.cache_seqlens[b] : p.capacity;
+  L = min(max(L, 0), p.capacity);
+  const int64_t pos = (int64_t)L + n;
+  if (pos >= p.capacity) return;
+  const int log_p = __builtin_ctz(pp.page_block_size);
+  int blk = pp.block_table[(int64_t)b * pp.block_table_stride + (pos >> log_p)];
+  blk = min(max(blk, 0), pp.num_blocks - 1);
+  const int64_t row = pos & (pp.page_block_size - 1);
+  const uint16_t* ks = (const uint16_t*)p.k_new + b * p.k_new_stride[0] + n * p.k_new_stride[1] + h * p.k_new_stride[2] + 8 * c;
+  const uint16_t* vs = (const uint16_t*)p.v_new + b * p.v_new_stride[0] + n * p.v_new_stride[1] + h * p.v_new_stride[2] + 8 * c;
+  uint16_t* kd = (uint16_t*)p.k_cache + blk * p.k_cache_stride[0] + row * p.k_cache_stride[1] + h * p.k_cache_stride[2] + 8 * c;
+  uint16_t* vd = (uint16_t*)p.v_cache + blk * p.v_cache_stride[0] + row * p.v_cache_stride[1] + h * p.v_cache_stride[2] + 8 * c;
+  const u32x4 kv = *(const u32x4*)ks, vv = *(const u32x4*)vs;
+  *(u32x4*)kd = kv;
+  *(u32x4*)vd = vv;
+}
+
 // Per output row (b, h, i), 64 threads (4 columns each), 4 rows per workgroup:
 //   m = max_s lse_s,  w_s = 2^(lse_s - m),  O = sum_s w_s O_s / sum_s w_s,  LSE2 = m + log2 sum_s w_s
 // summed in split order.  A split with lse_s = -inf (no visible key) has weight 0 and its partial O
@@ -71,6 +103,13 @@ hipError_t launch_kvcache_append(const fa2_kvcache_args& a, hipStream_t st) {
   const int64_t total = (int64_t)a.batch * a.seqlen_new * a.heads_kv * (a.head_dim >> 3);
   if (total <= 0) return hipSuccess;
   hipLaunchKernelGGL(kvcache_append_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_kvcache_paged_append(const fa2_paged_kvcache_args& a, hipStream_t st) {
+  const int64_t total = (int64_t)a.base.batch * a.base.seqlen_new * a.base.heads_kv * (a.base.head_dim >> 3);
+  if (total <= 0) return hipSuccess;
+  hipLaunchKernelGGL(kvcache_paged_append_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, a);
   return hipGetLastError();
 }
 

@@ -15,6 +15,10 @@ hipError_t launch_kvcache_split(const fa2_kvcache_args& a, int nsplit, hipStream
 // kvcache.hip: the append of k_new / v_new and the combination of nsplit > 1 partial results
 hipError_t launch_kvcache_append(const fa2_kvcache_args& a, hipStream_t st);
 hipError_t launch_kvcache_combine(const fa2_kvcache_args& a, int nsplit, hipStream_t st);
+// kvcache_paged_kernel.h and kvcache.hip: the same two over a paged cache (the combination is shared)
+template <bool BF16, int DT>
+hipError_t launch_kvcache_paged_split(const fa2_paged_kvcache_args& a, int nsplit, hipStream_t st);
+hipError_t launch_kvcache_paged_append(const fa2_paged_kvcache_args& a, hipStream_t st);
 
 // compute units of the current device, 256 (an MI355X) when there is none to ask
 inline int kv_cu_count() {

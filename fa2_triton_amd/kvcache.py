@@ -1,4 +1,6 @@
-"""KV-cache decode attention: `flash_attn_with_kvcache` (C ABI `fa2_fwd_kvcache`, ABI 10 minor 1).
+"""KV-cache decode attention: `flash_attn_with_kvcache` (C ABI `fa2_fwd_kvcache`, ABI 10 minor 1)
+over one contiguous cache slab per sequence, and `flash_attn_with_paged_kvcache`
+(`fa2_fwd_kvcache_paged`) over a pool of fixed-size blocks addressed through a block table.
 
 One query token, or a few, per sequence against a pre-allocated key / value cache whose sequences
 have their own filled lengths.  The lengths stay on the device: nothing here reads a tensor's
@@ -30,53 +32,21 @@ def _check_plain_args(k, v, window_size, num_splits, cache_seqlens) -> Tuple[int
     return min(max(left, -1), 2**30), min(max(right, -1), 2**30)
 
 
-def flash_attn_with_kvcache(
-    q: Tensor,
-    k_cache: Tensor,
-    v_cache: Tensor,
-    k: Optional[Tensor] = None,
-    v: Optional[Tensor] = None,
-    cache_seqlens: Union[None, int, Tensor] = None,
-    softmax_scale: Optional[float] = None,
-    causal: bool = False,
-    window_size: Tuple[int, int] = (-1, -1),
-    num_splits: int = 0,
-    return_lse: bool = False,
-):
-    """Attention of `q` [B, Sq, Hq, D] over the first L_b keys of `k_cache` / `v_cache`
-    [B, cap, Hkv, D] (fp16 or bf16, Hq % Hkv == 0, any strides with a unit head-dim stride).
-
-    Inference only: no autograd graph is built and the result never requires grad, whatever the
-    inputs require.  Not implemented: paged caches (block tables), rotary embedding, bias, dropout,
-    backward.
-
-    cache_seqlens: None (every sequence is `cap` long), a Python int, or an int32 device tensor [B]
-        that is read on the device; each value is clamped to [0, cap].  It is not modified.
-    k, v: optional new rows [B, Sn, Hkv, D], both or neither.  They are first written into the caches
-        at positions L_b .. L_b + Sn - 1 (rows at or past `cap` are dropped) and attention then runs
-        over min(L_b + Sn, cap) keys.
-    causal, window_size=(left, right): bottom-right aligned on the valid length.  With
-        diag = L_b - Sq, query i sees key j iff j < L_b and i + diag - left <= j <= i + diag + right;
-        a negative bound is no bound and causal forces right = 0.  Rows that see no key give 0.
-    num_splits: 0 lets the library choose how many ways the keys are split over workgroups (from
-        the shapes alone); 1 .. 128 forces the count.
-    return_lse: also return the base-2 log-sum-exp [B, Hq, Sq] in fp32 (-inf for rows that see no key).
-
-    Returns `out` [B, Sq, Hq, D] in q's dtype, or `(out, lse)`.
-    """
-    left, right = _check_plain_args(k, v, window_size, num_splits, cache_seqlens)
+def _check_tensors(q, k_cache, v_cache, k, v, cache_shape: str):
+    """The checks both cache layouts share: q, the two caches and the optional new rows.  Returns
+    (batch, seqlen_q, heads_q, head_dim, heads_kv, new) with `new` the (name, tensor) pairs of k, v."""
     for name, t in (("q", q), ("k_cache", k_cache), ("v_cache", v_cache)):
         if not isinstance(t, Tensor) or t.dim() != 4:
-            raise ValueError(f"{name} must be a 4-d tensor [batch, seqlen, heads, head_dim]")
+            raise ValueError(f"{name} must be a 4-d tensor [{'batch, seqlen' if name == 'q' else cache_shape}, heads, head_dim]")
     batch, seqlen_q, heads_q, head_dim = q.shape
-    _, cap, heads_kv, _ = k_cache.shape
-    if k_cache.shape != (batch, cap, heads_kv, head_dim) or v_cache.shape != k_cache.shape:
-        raise ValueError(f"{k_cache.shape = } and {v_cache.shape = } must both be (batch={batch}, cap, heads_kv, "
-                         f"head_dim={head_dim})")
+    lead, rows, heads_kv, _ = k_cache.shape
+    if k_cache.shape[3] != head_dim or (cache_shape == "batch, cap" and lead != batch) or v_cache.shape != k_cache.shape:
+        raise ValueError(f"{k_cache.shape = } and {v_cache.shape = } must both be ({cache_shape}, heads_kv, "
+                         f"head_dim={head_dim}) with batch={batch}")
     if heads_kv < 1 or heads_q % heads_kv != 0:
         raise ValueError(f"{heads_q = } is not divisible by {heads_kv = }")
-    if seqlen_q < 1 or cap < 1:
-        raise ValueError(f"{seqlen_q = } and the cache capacity {cap} must be at least 1")
+    if seqlen_q < 1 or rows < 1 or lead < 1:
+        raise ValueError(f"{seqlen_q = } and the cache sizes {lead} x {rows} must be at least 1")
     new = () if k is None else (("k", k), ("v", v))
     for name, t in new:
         if not isinstance(t, Tensor) or t.dim() != 4 or t.shape != (batch, t.shape[1], heads_kv, head_dim) or t.shape[1] < 1:
@@ -96,45 +66,167 @@ def flash_attn_with_kvcache(
             raise ValueError(f"{name} must have a unit head-dim stride")
     if head_dim > 256:
         raise NotImplementedError(f"{head_dim = } > 256 is not supported")
-    if isinstance(cache_seqlens, Tensor):
-        if cache_seqlens.dtype != torch.int32 or cache_seqlens.shape != (batch,) or cache_seqlens.device != q.device:
-            raise ValueError(f"cache_seqlens must be an int32 tensor of shape ({batch},) on {q.device}, got "
-                             f"{cache_seqlens.dtype} {tuple(cache_seqlens.shape)} on {cache_seqlens.device}")
-        seqlens = cache_seqlens.contiguous()
-    elif cache_seqlens is None:
-        seqlens = None
-    else:
-        seqlens = torch.full((batch,), min(max(cache_seqlens, 0), cap), dtype=torch.int32, device=q.device)
-    softmax_scale = 1.0 / math.sqrt(head_dim) if softmax_scale is None else float(softmax_scale)
+    return batch, seqlen_q, heads_q, head_dim, heads_kv, new
 
+
+def _seqlens_on_device(cache_seqlens, batch: int, cap: int, device) -> Optional[Tensor]:
+    if isinstance(cache_seqlens, Tensor):
+        if cache_seqlens.dtype != torch.int32 or cache_seqlens.shape != (batch,) or cache_seqlens.device != device:
+            raise ValueError(f"cache_seqlens must be an int32 tensor of shape ({batch},) on {device}, got "
+                             f"{cache_seqlens.dtype} {tuple(cache_seqlens.shape)} on {cache_seqlens.device}")
+        return cache_seqlens.contiguous()
+    if cache_seqlens is None:
+        return None
+    return torch.full((batch,), min(max(cache_seqlens, 0), cap), dtype=torch.int32, device=device)
+
+
+def _run(args, base, workspace_bytes, entry, q, k_cache, v_cache, new, seqlens, cap, softmax_scale, causal, left, right,
+         num_splits, return_lse):
+    """Fill `base` (the fa2_kvcache_args of `args`: `args` itself, or its first member), allocate the
+    outputs and the workspace, and launch `entry(args, stream)` on q's stream."""
+    batch, seqlen_q, heads_q, head_dim = q.shape
     with torch.no_grad():
         out = torch.empty(q.shape, dtype=q.dtype, device=q.device)
         lse = torch.empty((batch, heads_q, seqlen_q), dtype=torch.float32, device=q.device) if return_lse else None
-        args = _lib.KvCacheArgs()
-        args.q, args.k_cache, args.v_cache, args.o = q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), out.data_ptr()
-        args.lse = lse.data_ptr() if return_lse else None
-        args.q_stride[:] = bshd_strides(q)
-        args.k_cache_stride[:] = bshd_strides(k_cache)
-        args.v_cache_stride[:] = bshd_strides(v_cache)
-        args.o_stride[:] = bshd_strides(out)
+        base.q, base.k_cache, base.v_cache, base.o = q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), out.data_ptr()
+        base.lse = lse.data_ptr() if return_lse else None
+        base.q_stride[:] = bshd_strides(q)
+        base.k_cache_stride[:] = bshd_strides(k_cache)
+        base.v_cache_stride[:] = bshd_strides(v_cache)
+        base.o_stride[:] = bshd_strides(out)
         if new:
-            args.k_new, args.v_new = k.data_ptr(), v.data_ptr()
-            args.k_new_stride[:] = bshd_strides(k)
-            args.v_new_stride[:] = bshd_strides(v)
-            args.seqlen_new = k.shape[1]
-        args.cache_seqlens = seqlens.data_ptr() if seqlens is not None else None
-        args.batch, args.heads_q, args.heads_kv = batch, heads_q, heads_kv
-        args.seqlen_q, args.capacity, args.head_dim = seqlen_q, cap, head_dim
-        args.causal = int(bool(causal))
-        args.window_left, args.window_right = left, right
-        args.dtype = encode_dtype(q)
-        args.num_splits = num_splits
-        args.softmax_scale = softmax_scale
-        lib = _lib.load()
-        need = lib.fa2_kvcache_workspace_bytes(ctypes.byref(args))
+            (_, k), (_, v) = new
+            base.k_new, base.v_new = k.data_ptr(), v.data_ptr()
+            base.k_new_stride[:] = bshd_strides(k)
+            base.v_new_stride[:] = bshd_strides(v)
+            base.seqlen_new = k.shape[1]
+        base.cache_seqlens = seqlens.data_ptr() if seqlens is not None else None
+        base.batch, base.heads_q, base.heads_kv = batch, heads_q, k_cache.shape[2]
+        base.seqlen_q, base.capacity, base.head_dim = seqlen_q, cap, head_dim
+        base.causal = int(bool(causal))
+        base.window_left, base.window_right = left, right
+        base.dtype = encode_dtype(q)
+        base.num_splits = num_splits
+        base.softmax_scale = 1.0 / math.sqrt(head_dim) if softmax_scale is None else float(softmax_scale)
+        need = workspace_bytes(ctypes.byref(args))
         workspace = None
         if need > 0:  # a function of the shapes only
             workspace = torch.empty(need, dtype=torch.uint8, device=q.device)
-            args.workspace, args.workspace_bytes = workspace.data_ptr(), need
-        _lib.check(launch_on(q, lambda st: lib.fa2_fwd_kvcache(ctypes.byref(args), st)))
+            base.workspace, base.workspace_bytes = workspace.data_ptr(), need
+        _lib.check(launch_on(q, lambda st: entry(ctypes.byref(args), st)))
     return (out, lse) if return_lse else out
+
+
+def flash_attn_with_kvcache(
+    q: Tensor,
+    k_cache: Tensor,
+    v_cache: Tensor,
+    k: Optional[Tensor] = None,
+    v: Optional[Tensor] = None,
+    cache_seqlens: Union[None, int, Tensor] = None,
+    softmax_scale: Optional[float] = None,
+    causal: bool = False,
+    window_size: Tuple[int, int] = (-1, -1),
+    num_splits: int = 0,
+    return_lse: bool = False,
+):
+    """Attention of `q` [B, Sq, Hq, D] over the first L_b keys of `k_cache` / `v_cache`
+    [B, cap, Hkv, D] (fp16 or bf16, Hq % Hkv == 0, any strides with a unit head-dim stride).
+
+    Inference only: no autograd graph is built and the result never requires grad, whatever the
+    inputs require.  For paged caches (a pool of blocks and a block table) see
+    `flash_attn_with_paged_kvcache`.  Not implemented: rotary embedding, bias, dropout, backward.
+
+    cache_seqlens: None (every sequence is `cap` long), a Python int, or an int32 device tensor [B]
+        that is read on the device; each value is clamped to [0, cap].  It is not modified.
+    k, v: optional new rows [B, Sn, Hkv, D], both or neither.  They are first written into the caches
+        at positions L_b .. L_b + Sn - 1 (rows at or past `cap` are dropped) and attention then runs
+        over min(L_b + Sn, cap) keys.
+    causal, window_size=(left, right): bottom-right aligned on the valid length.  With
+        diag = L_b - Sq, query i sees key j iff j < L_b and i + diag - left <= j <= i + diag + right;
+        a negative bound is no bound and causal forces right = 0.  Rows that see no key give 0.
+    num_splits: 0 lets the library choose how many ways the keys are split over workgroups (from
+        the shapes alone); 1 .. 128 forces the count.
+    return_lse: also return the base-2 log-sum-exp [B, Hq, Sq] in fp32 (-inf for rows that see no key).
+
+    Returns `out` [B, Sq, Hq, D] in q's dtype, or `(out, lse)`.
+    """
+    left, right = _check_plain_args(k, v, window_size, num_splits, cache_seqlens)
+    batch, _, _, _, _, new = _check_tensors(q, k_cache, v_cache, k, v, "batch, cap")
+    cap = k_cache.shape[1]
+    seqlens = _seqlens_on_device(cache_seqlens, batch, cap, q.device)
+    lib = _lib.load()
+    args = _lib.KvCacheArgs()
+    return _run(args, args, lib.fa2_kvcache_workspace_bytes, lib.fa2_fwd_kvcache, q, k_cache, v_cache, new, seqlens, cap,
+                softmax_scale, causal, left, right, num_splits, return_lse)
+
+
+def flash_attn_with_paged_kvcache(
+    q: Tensor,
+    k_cache: Tensor,
+    v_cache: Tensor,
+    block_table: Tensor,
+    cache_seqlens: Union[int, Tensor],
+    k: Optional[Tensor] = None,
+    v: Optional[Tensor] = None,
+    softmax_scale: Optional[float] = None,
+    causal: bool = False,
+    window_size: Tuple[int, int] = (-1, -1),
+    num_splits: int = 0,
+    return_lse: bool = False,
+):
+    """`flash_attn_with_kvcache` over a paged cache: `k_cache` / `v_cache` are pools
+    [num_blocks, page_block_size, Hkv, D] (any strides with a unit head-dim stride, so a pool stored
+    [N, Hkv, P, D] and viewed [N, P, Hkv, D] needs no copy) and logical key j of batch b is row
+    j % P of block `block_table[b, j // P]`.  P is a power of two >= 16.
+
+    Inference only, as the contiguous function.  Not implemented: rotary embedding, a batch-index
+    indirection, fp8 caches, page sizes that are not powers of two, bias, dropout, backward.
+
+    block_table: int32 device tensor [B, max_blocks] with a unit stride in its last dimension (a
+        column slice of a wider table is fine).  The capacity of a sequence is max_blocks * P.
+        Entries of pages at or past ceil(L_b / P) (after the append) are never read and may hold
+        anything; an entry that is read is clamped into [0, num_blocks - 1] on the device, so a wrong
+        table reads or writes a wrong block of the pool, never memory outside it.  Rows may share
+        blocks (a common prefix) as long as the call does not append into a shared block: writing
+        through tables that alias is the caller's error.  It is not modified.
+    cache_seqlens: required: an int32 device tensor [B] read on the device, or a Python int; each
+        value is clamped to [0, max_blocks * P].  It is not modified.
+    k, v: optional new rows [B, Sn, Hkv, D]; row n of batch b is written to logical position L_b + n
+        through the table (positions at or past the capacity are dropped).  The blocks must already
+        be in the table: nothing is allocated here.
+    softmax_scale, causal, window_size, num_splits, return_lse: as `flash_attn_with_kvcache`; the
+        split count is the same function of the same shapes, with cap = max_blocks * P.
+
+    Returns `out` [B, Sq, Hq, D] in q's dtype, or `(out, lse)`; the same bits as the contiguous
+    function on the gathered cache.
+    """
+    if cache_seqlens is None:
+        raise TypeError("cache_seqlens is required with a paged cache: an int or an int32 tensor")
+    left, right = _check_plain_args(k, v, window_size, num_splits, cache_seqlens)
+    if not isinstance(block_table, Tensor) or block_table.dim() != 2:
+        raise ValueError("block_table must be a 2-d int32 tensor [batch, max_blocks]")
+    batch, _, _, _, _, new = _check_tensors(q, k_cache, v_cache, k, v, "num_blocks, page_block_size")
+    num_blocks, page = k_cache.shape[0], k_cache.shape[1]
+    if page < 16 or page & (page - 1):
+        raise ValueError(f"page_block_size (k_cache.shape[1] = {page}) must be a power of two >= 16")
+    if block_table.dtype != torch.int32:
+        raise TypeError(f"block_table must be int32, got {block_table.dtype}")
+    if block_table.shape[0] != batch or block_table.shape[1] < 1:
+        raise ValueError(f"block_table must be [batch={batch}, max_blocks >= 1], got {tuple(block_table.shape)}")
+    if block_table.device != q.device:
+        raise ValueError(f"block_table must be on q's GPU device, got {block_table.device}")
+    if block_table.stride(1) != 1 and block_table.shape[1] > 1:
+        raise ValueError("block_table must have a unit stride in its last dimension")
+    max_blocks = block_table.shape[1]
+    cap = max_blocks * page
+    if cap > 2**30:
+        raise NotImplementedError(f"max_blocks * page_block_size = {cap} > 2^30 is not supported")
+    seqlens = _seqlens_on_device(cache_seqlens, batch, cap, q.device)
+    lib = _lib.load()
+    args = _lib.PagedKvCacheArgs()
+    args.block_table = block_table.data_ptr()
+    args.block_table_stride = block_table.stride(0) if batch > 1 else max(block_table.stride(0), max_blocks)
+    args.page_block_size, args.num_blocks = page, num_blocks
+    return _run(args, args.base, lib.fa2_paged_kvcache_workspace_bytes, lib.fa2_fwd_kvcache_paged, q, k_cache, v_cache,
+                new, seqlens, cap, softmax_scale, causal, left, right, num_splits, return_lse)

@@ -202,7 +202,8 @@ int fa2_bwd_stages_ex(const fa2_bwd_args* args, int stages, const fa2_policy* po
 /* KV-cache decode attention (ABI 10, minor 1): O = softmax(scale * Q K^T, masks) V for a few query
  * tokens against a pre-allocated key / value cache whose sequences have their own filled lengths,
  * read on the device (no host synchronisation; the call can be captured in a graph).  Forward
- * only.  Not implemented: paged caches (block tables), rotary embedding, bias, dropout, backward.
+ * only.  Paged caches (block tables): fa2_fwd_kvcache_paged below.  Not implemented: rotary
+ * embedding, bias, dropout, backward.
  *
  *  - L_b, the valid keys of batch b: cache_seqlens[b] clamped to [0, capacity] (NULL: capacity);
  *    with k_new / v_new, min(that + seqlen_new, capacity) after the new rows n = 0 .. seqlen_new - 1
@@ -256,6 +257,37 @@ int fa2_kvcache_num_splits(const fa2_kvcache_args* args);
 /* Bytes of workspace: 0 with one split, else nsplit * B * Hq * Sq * (D + 1) * 4 (the fp32 partial
  * outputs [nsplit, B, Hq, Sq, D] followed by the partial LSE2 [nsplit, B, Hq, Sq]). */
 int64_t fa2_kvcache_workspace_bytes(const fa2_kvcache_args* args);
+
+/* The same attention over a paged cache (added within ABI 10 minor 1: detect it by the presence of
+ * the symbol fa2_fwd_kvcache_paged).  k_cache / v_cache of `base` are pools of blocks
+ * [num_blocks, page_block_size, Hkv, D] and logical key j of batch b is row j % P of block
+ * block_table[b, j / P] (P = page_block_size).  In `base`:
+ *  - k_cache_stride / v_cache_stride are the (block, row-in-block, head) strides, in elements;
+ *  - capacity = max_blocks * P, the keys a row of the table can address; max_blocks is not stated
+ *    separately, it is capacity / P (capacity % P != 0 is rejected).
+ * Everything else is fa2_fwd_kvcache's semantics with that capacity: L_b clamped to [0, capacity],
+ * the bottom-right aligned masks, the append (row n of batch b goes to logical position L_b + n
+ * through the table; positions >= capacity are dropped; the blocks must already be in the table),
+ * the split count and the workspace (the same functions of the same shapes).
+ *  - table entries of pages at or past ceil(L_b / P) (L_b after the append) are never read and may
+ *    hold anything; an entry that is read is clamped into [0, num_blocks - 1] on the device, so a
+ *    wrong table reads or writes a wrong block of the pool, never memory outside it.
+ *  - several table rows may name the same block (shared prefixes) as long as the call does not
+ *    append into it: appending through tables that alias is the caller's error.
+ *  - neither block_table nor cache_seqlens is modified. */
+typedef struct fa2_paged_kvcache_args {
+  fa2_kvcache_args base;
+  const int32_t* block_table;  /* [B, max_blocks] device int32, unit stride in the last dimension */
+  int64_t block_table_stride;  /* elements between batch rows, >= max_blocks */
+  int32_t page_block_size;     /* P: a power of two >= 16 */
+  int32_t num_blocks;          /* blocks in each pool, >= 1 */
+} fa2_paged_kvcache_args;
+
+int fa2_fwd_kvcache_paged(const fa2_paged_kvcache_args* args, void* stream);
+/* fa2_kvcache_num_splits / fa2_kvcache_workspace_bytes of args->base: a paged call and a
+ * contiguous call of the same shapes use the same split count and workspace. */
+int fa2_paged_kvcache_num_splits(const fa2_paged_kvcache_args* args);
+int64_t fa2_paged_kvcache_workspace_bytes(const fa2_paged_kvcache_args* args);
 
 const char* fa2_last_error(void);
 int fa2_version(void);

@@ -12,7 +12,14 @@ fraction of the copy bandwidth bench_micro/hbm_copy.hip measures on the same box
 runs that binary first; --copy-gbps passes a figure).  Shapes whose K + V footprint is under the
 256 MiB last-level cache are marked: their figure is a cache figure, not an HBM one.
 
-usage: python scripts/bench_decode.py [--rounds N] [--iters N] [--hbm-copy-bin PATH | --copy-gbps X] [--out FILE]
+--page-block-size P [P ...] adds, per shape and per P, a "paged_pP" variant: flash_attn_with_paged_kvcache
+over a pool holding the same keys and values in blocks of P rows, placed by a shuffled block table.
+It is timed in the same alternation and reported as paged_over_kvcache[P], next to the round spread
+of both variants, which is the margin of that ratio.  --page-order identity leaves the blocks in
+place (table[b, j] = b * max_blocks + j).  Without --page-block-size the output is unchanged.
+
+usage: python scripts/bench_decode.py [--rounds N] [--iters N] [--hbm-copy-bin PATH | --copy-gbps X]
+                                      [--page-block-size P [P ...]] [--page-order shuffled|identity] [--out FILE]
 """
 import argparse
 import ctypes
@@ -26,7 +33,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from fa2_triton_amd import _lib as L  # noqa: E402
-from fa2_triton_amd import flash_attn_func, flash_attn_with_kvcache  # noqa: E402
+from fa2_triton_amd import flash_attn_func, flash_attn_with_kvcache, flash_attn_with_paged_kvcache  # noqa: E402
 
 SHAPES = ((1, 8192), (1, 131072), (8, 32768), (64, 8192))
 HQ, HKV, D = 32, 8, 128
@@ -61,12 +68,27 @@ def split_count(batch, cap):
     return L.load().fa2_kvcache_num_splits(ctypes.byref(a))
 
 
+def paged_copy(kc, vc, page, order):
+    """(k_pool, v_pool, table): the caches [B, cap, Hkv, D] cut into blocks of `page` rows that a
+    random permutation scatters over pools of exactly B * cap / page blocks (order "identity":
+    left in place, which separates the cost of the lookup from the cost of scattered addresses)."""
+    batch, cap, hkv, d = kc.shape
+    n = batch * cap // page
+    ids = torch.randperm(n, device=kc.device) if order == "shuffled" else torch.arange(n, device=kc.device)
+    kp, vp = torch.empty((n, page, hkv, d), dtype=kc.dtype, device=kc.device), torch.empty((n, page, hkv, d), dtype=kc.dtype, device=kc.device)
+    kp[ids] = kc.reshape(n, page, hkv, d)
+    vp[ids] = vc.reshape(n, page, hkv, d)
+    return kp, vp, ids.reshape(batch, cap // page).to(torch.int32)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--hbm-copy-bin", default=None)
     ap.add_argument("--copy-gbps", type=float, default=None)
+    ap.add_argument("--page-block-size", type=int, nargs="+", default=[])
+    ap.add_argument("--page-order", choices=("shuffled", "identity"), default="shuffled")
     ap.add_argument("--out", default=None)
     args = ap.parse_args(argv)
     copy_gbps = measured_copy_gbps(args.hbm_copy_bin) if args.hbm_copy_bin else args.copy_gbps
@@ -81,6 +103,10 @@ def main(argv=None):
         vc = torch.empty(batch, cap, HKV, D, device="cuda", dtype=torch.bfloat16).normal_(0.0, 0.5)
         variants = {"kvcache": lambda: flash_attn_with_kvcache(q, kc, vc),
                     "baseline": lambda: flash_attn_func(q, kc, vc)}
+        for page in args.page_block_size:
+            kp, vp, table = paged_copy(kc, vc, page, args.page_order)
+            variants[f"paged_p{page}"] = (lambda kp=kp, vp=vp, table=table:
+                                          flash_attn_with_paged_kvcache(q, kp, vp, table, cap))
         samples = {n: [] for n in variants}
         with torch.no_grad():
             for fn in variants.values():
@@ -93,6 +119,11 @@ def main(argv=None):
         ms = {n: med(samples[n]) for n in variants}
         kv_bytes = 2 * batch * cap * HKV * D * 2
         gbps = kv_bytes / (ms["kvcache"] * 1e-3) / 1e9
+        if args.page_block_size:
+            ref = flash_attn_with_kvcache(q, kc, vc)
+            for page in args.page_block_size:
+                if not torch.equal(variants[f"paged_p{page}"](), ref):
+                    raise SystemExit(f"paged P={page} differs from the contiguous result at B={batch} L={cap}")
         shapes.append({
             "B": batch, "L": cap, "num_splits": split_count(batch, cap),
             "ms": {n: round(ms[n], 5) for n in variants},
@@ -102,10 +133,15 @@ def main(argv=None):
             "kv_GBps": round(gbps, 1),
             "frac_of_copy_bandwidth": round(gbps / copy_gbps, 4) if copy_gbps else None,
         })
-        del q, kc, vc
+        if args.page_block_size:
+            shapes[-1]["paged_over_kvcache"] = {str(p): round(ms[f"paged_p{p}"] / ms["kvcache"], 4)
+                                                for p in args.page_block_size}
+        del q, kc, vc, variants
         torch.cuda.empty_cache()
     result = {"bench": "decode", "device": torch.cuda.get_device_name(0), "dtype": "bf16", "Hq": HQ, "Hkv": HKV, "D": D,
               "Sq": 1, "rounds": args.rounds, "iters": args.iters, "copy_GBps": copy_gbps, "shapes": shapes}
+    if args.page_block_size:
+        result["page_block_sizes"], result["page_order"] = args.page_block_size, args.page_order
     line = json.dumps(result)
     print(line, flush=True)
     if args.out:
