@@ -1,4 +1,4 @@
-// SDWA byte sign-extension on gfx950 (dev check behind hp_gen.py FwdGen.mask_and / mask_prep_items):
+// SDWA byte sign-extension on gfx950 (dev check behind hp_gen/fwd.py FwdGen.mask_and / mask_prep_items):
 // sext(byte) keeps the byte's low 7 bits (0x80 -> 0xFFFFFF80), so the AND masks must be whole
 // 0x00 / 0xFF bytes; the v_perm_b32 sign selectors (0x0B090A08 on S0 = W << (7 - c),
 // S1 = W << (15 - c)) build byte n = bit c + 8 n of W ? 0xFF : 0x00.

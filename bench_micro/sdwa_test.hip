@@ -1,4 +1,4 @@
-// SDWA semantics on gfx950 (dev check behind hp_gen.py DkdvGen.pack_keep): an op with
+// SDWA semantics on gfx950 (dev check behind hp_gen/dkdv.py DkdvGen.pack_keep): an op with
 // dst_sel:WORD_1 writes the LOW 16 bits of its result into the destination's high word, so the
 // sources must select WORD_1 too.  build: hipcc --offload-arch=gfx950 -O2 bench_micro/sdwa_test.hip -o bench_micro/sdwa_test
 #include <hip/hip_runtime.h>

@@ -97,7 +97,7 @@ def generated_sources():
 
 
 def generated_headers():
-    """The hand-placed instruction streams (hp_gen.py -> csrc/gen/*.h), rewritten only on change."""
+    """The hand-placed instruction streams (hp_gen/ -> csrc/gen/*.h), rewritten only on change."""
     sys.path.insert(0, os.path.dirname(HERE))
     try:
         from fa2_triton_amd import hp_gen
@@ -109,7 +109,8 @@ def generated_headers():
 def deps_mtime() -> float:
     files = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".hip"))]
     files += [os.path.join(GEN, f) for f in os.listdir(GEN) if f.endswith(".h")]
-    files.append(os.path.join(HERE, "hp_gen.py"))
+    hp_gen = os.path.join(HERE, "hp_gen")
+    files += [os.path.join(hp_gen, f) for f in os.listdir(hp_gen) if f.endswith(".py")]
     files.append(os.path.join(INCLUDE, "fa2_amd.h"))
     files.append(os.path.abspath(__file__))
     return max(os.path.getmtime(f) for f in files)
@@ -144,11 +145,11 @@ DEFAULT_LIB = os.path.join(HERE, "libfa2_amd.so")
 
 
 def check_dev_env():
-    """Development builds (timing ablations FA2_HPGEN_ABL, whose outputs are wrong; the stamp or
-    dev variants -DFA2_HP_STAMPS / -DFA2_HP_DEV) never overwrite the shipped library or its objects."""
+    """Development builds (timing ablations FA2_HPGEN_ABL, whose outputs are wrong; the stamp
+    variant -DFA2_HP_STAMPS) never overwrite the shipped library or its objects."""
     dev = [k for k in ("FA2_HPGEN_ABL",) if os.environ.get(k)]
     flags = os.environ.get("FA2_HIPCC_FLAGS", "")
-    dev += [f for f in ("FA2_HP_STAMPS", "FA2_HP_DEV") if f in flags]
+    dev += [f for f in ("FA2_HP_STAMPS",) if f in flags]
     if dev and (os.path.abspath(LIB) == os.path.abspath(DEFAULT_LIB) or
                 os.path.abspath(OBJ) == os.path.abspath(os.path.join(HERE, "_build"))):
         raise RuntimeError(f"development build ({', '.join(dev)}) must set FA2_LIB_OUT and FA2_BUILD_DIR away from "

@@ -53,6 +53,10 @@ def export(liger_root: str, with_lib: bool = True, force: bool = False) -> list:
     for name in sorted(os.listdir(PKG)):
         if name.endswith(".py") or (with_lib and name == "libfa2_amd.so"):
             put(os.path.join(PKG, name), os.path.join(dst, name))
+    os.makedirs(os.path.join(dst, "hp_gen"), exist_ok=True)
+    for name in sorted(os.listdir(os.path.join(PKG, "hp_gen"))):
+        if name.endswith(".py"):  # the generator of csrc/gen/*_hp_body.h, which build.py runs
+            put(os.path.join(PKG, "hp_gen", name), os.path.join(dst, "hp_gen", name))
     for name in sorted(os.listdir(os.path.join(PKG, "csrc"))):
         if name.endswith((".h", ".hip")):  # generated per-instantiation units are rebuilt by build.py
             put(os.path.join(PKG, "csrc", name), os.path.join(dst, "csrc", name))

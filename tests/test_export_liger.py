@@ -17,6 +17,7 @@ def test_export_imports_as_liger_op(tmp_path):
     dst = tmp_path / "src" / "liger_kernel" / "ops" / "flash_attention"
     assert str(dst / "wrapper.py") in out and (dst / "include" / "fa2_amd.h").exists()
     assert (dst / "csrc" / "bwd_kernel.h").exists() and (dst / "build.py").exists()
+    assert all((dst / "hp_gen" / m).exists() for m in ("__init__.py", "__main__.py", "emitter.py", "fwd.py", "dq.py", "dkdv.py"))
     assert not any("oracle" in p or "tests" in p for p in out)
     code = (
         "import sys; sys.path.insert(0, %r)\n"
