@@ -74,11 +74,14 @@ def attention_reference(
     softcap: float = 0.0,
     upcast: bool = True,
     reorder_ops: bool = False,
+    softmax_scale: Optional[float] = None,
 ) -> Tensor:
     """Dense attention; see the module docstring for the exact semantics.
 
     Same argument list and meaning as `flash_attn_reference`
-    (/root/reference/src/reference_implementation.py:38-52).
+    (/root/reference/src/reference_implementation.py:38-52), plus `softmax_scale` (beyond the
+    reference, which fixes 1 / sqrt(D)): the factor on q k^T; None keeps 1 / sqrt(D) and every
+    operation as it was.
     """
     if causal:
         window_size = (window_size[0], 0)
@@ -91,7 +94,7 @@ def attention_reference(
     k = torch.repeat_interleave(k, group, dim=2)
     v = torch.repeat_interleave(v, group, dim=2)
 
-    inv = 1.0 / math.sqrt(d)
+    inv = 1.0 / math.sqrt(d) if softmax_scale is None else float(softmax_scale)
     if reorder_ops:
         scores = torch.einsum("bqhd,bkhd->bhqk", q, k * inv)
     else:

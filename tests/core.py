@@ -26,6 +26,116 @@ def generate_test_data(batch_size, nheads_q, nheads_kv, seqlen_q, seqlen_k, head
     return q.requires_grad_(), k.requires_grad_(), v.requires_grad_(), do
 
 
+STAIR_EDGES_ALIGNED = (64, 128, 192)  # a new level at every 64-key tile
+STAIR_EDGES_MID = (37, 101, 165)  # levels change inside the tiles
+STAIR_A = 4.0  # q column 0 of the planted rows
+
+
+def stair_levels(seqlen_k: int, edges, descending=False, valid_lens=None, batch_size=1, device="cpu") -> Tensor:
+    """[B, Sk] int64: level(j) = the number of entries of `edges` (truncated to Sk) that are <= j.
+    `descending` reverses the staircase along each sequence's valid keys, level(L_b - 1 - j) for
+    j < L_b and 0 past them; ascending it runs over the whole (padded) length whatever L_b is."""
+    edges = torch.tensor([e for e in edges if e < seqlen_k], dtype=torch.long, device=device)
+    j = torch.arange(seqlen_k, device=device)
+    lens = torch.tensor(list(valid_lens) if valid_lens is not None else [seqlen_k] * batch_size, device=device)
+    if not descending:
+        return (j[:, None] >= edges[None, :]).sum(-1)[None, :].expand(lens.numel(), -1).contiguous()
+    jr = lens[:, None] - 1 - j[None, :]  # [B, Sk], negative past the valid keys
+    return ((jr[:, :, None] >= edges[None, None, :]).sum(-1) * (jr >= 0)).contiguous()
+
+
+def planted_row_mask(seqlen_q: int, planted_rows, device="cpu") -> Tensor:
+    """[Sq] bool: "third" (i % 3 == 0: planted and control rows inside every wave) or a range
+    (first, last + 1), e.g. (64, 128): the 64 rows of one wave, whose neighbours never vote."""
+    i = torch.arange(seqlen_q, device=device)
+    if planted_rows == "third":
+        return i % 3 == 0
+    lo, hi = planted_rows
+    return (i >= lo) & (i < hi)
+
+
+def generate_staircase_data(batch_size, nheads_q, nheads_kv, seqlen_q, seqlen_k, head_dim, dtype, edges, step,
+                            planted_rows="third", descending=False, softmax_scale=None, valid_lens=None, seed=0,
+                            device="cuda"):
+    """generate_test_data with a staircase planted in head-dim column 0, so that the running row
+    max of the planted rows climbs by `step` log2 units per level -- beyond kDeferMax (csrc/common.h),
+    which the N(0, 0.5) inputs never do after the first tile.
+
+    q[:, planted, :, 0] = STAIR_A, q[:, others, :, 0] = 0 (control rows keep the flat softmax);
+    k[b, j, :, 0] = level_b(j) c with c = step / (log2e STAIR_A scale) rounded to the dtype and
+    `scale` the call's softmax scale, so the planted rows get level(j) step log2 units on top of
+    their scores.  Returns (q, k, v, do, levels [B, Sk], planted [Sq])."""
+    from oracle.reference import LOG2E
+
+    q, k, v, do = generate_test_data(batch_size, nheads_q, nheads_kv, seqlen_q, seqlen_k, head_dim, dtype, seed, device)
+    scale = head_dim ** -0.5 if softmax_scale is None else softmax_scale
+    levels = stair_levels(seqlen_k, edges, descending, valid_lens, batch_size, device)
+    planted = planted_row_mask(seqlen_q, planted_rows, device)
+    c = torch.tensor(step / (LOG2E * STAIR_A * scale), dtype=dtype, device=device)
+    with torch.no_grad():
+        q[:, :, :, 0] = (planted.to(dtype) * STAIR_A)[None, :, None]
+        k[:, :, :, 0] = (levels.to(dtype) * c)[:, :, None]
+    return q, k, v, do, levels, planted
+
+
+def staircase_growth(scores2: Tensor, valid_lens=None, threshold: float = 8.0):
+    """What a forward that defers its running max meets, from fp32 scores in log2 units
+    [B, H, Sq, Sk] (bias included): 64-key blocks from key 0 of each sequence's valid keys; a row's
+    max starts at its first block's and moves to a later block's max only when that outgrows the
+    stale max by more than `threshold`.  Returns (growth [B, H, Sq, nblk - 1]: block max minus the
+    stale max it met, -inf for blocks past the valid keys; moved: growth > threshold)."""
+    b, h, sq, sk = scores2.shape
+    s = scores2.float()
+    if valid_lens is not None:
+        lens = torch.tensor(list(valid_lens), device=s.device)
+        s = s.masked_fill((torch.arange(sk, device=s.device)[None, :] >= lens[:, None])[:, None, None, :], float("-inf"))
+    nblk = (sk + 63) // 64
+    s = torch.nn.functional.pad(s, (0, nblk * 64 - sk), value=float("-inf"))
+    bm = s.view(b, h, sq, nblk, 64).amax(-1)
+    stale = bm[..., 0].clone()
+    growth = []
+    for i in range(1, nblk):
+        g = bm[..., i] - stale
+        growth.append(g)
+        stale = torch.where(g > threshold, bm[..., i], stale)
+    growth = torch.stack(growth, -1) if growth else s.new_empty(b, h, sq, 0)
+    return growth, growth > threshold
+
+
+def check_staircase_precondition(scores2: Tensor, levels: Tensor, planted: Tensor, step: float, valid_lens=None) -> dict:
+    """The staircase's condition on the input, from the oracle's fp32 scores alone (log2 units):
+    at every 64-key block where the planted levels say the stale max is outgrown by more than 8
+    (level difference x step against the level the max last moved to), EVERY planted row's block
+    max exceeds its stale max by more than 8.5; at every other block it stays below 8; and no control
+    row ever outgrows its stale max by more than 8.  Returns the extreme figures."""
+    growth, _ = staircase_growth(scores2, valid_lens)
+    b, sk = levels.shape
+    nblk = (sk + 63) // 64
+    lens = list(valid_lens) if valid_lens is not None else [sk] * b
+    report = {"planted_min_move": float("inf"), "planted_max_stay": float("-inf"), "control_max": float("-inf"), "moves": 0}
+    for bi in range(b):
+        lv = levels[bi, : lens[bi]].tolist()
+        top = [max(lv[i * 64:(i + 1) * 64]) for i in range((lens[bi] + 63) // 64)]
+        stale = top[0] if top else 0
+        for i in range(1, nblk):
+            g = growth[bi, :, :, i - 1]  # [H, Sq]
+            gp, gc = g[:, planted], g[:, ~planted]
+            if gc.numel():
+                report["control_max"] = max(report["control_max"], gc.max().item())
+            if not gp.numel():
+                continue
+            if i < len(top) and (top[i] - stale) * step > 8.0:
+                stale = top[i]
+                report["moves"] += 1
+                report["planted_min_move"] = min(report["planted_min_move"], gp.min().item())
+            else:
+                report["planted_max_stay"] = max(report["planted_max_stay"], gp.max().item())
+    assert report["planted_min_move"] > 8.5, report
+    assert report["planted_max_stay"] < 8.0, report
+    assert report["control_max"] <= 8.0, report
+    return report
+
+
 def generate_attention_mask(x: Tensor) -> Tensor:
     """Random right padding per batch row, one row unpadded (reference tests/utils.py:40-56)."""
     mask = torch.ones(size=x.shape[:2], dtype=torch.bool, device=x.device)

@@ -34,35 +34,37 @@ def _key_mask(lens, cap):
     return torch.arange(cap, device="cuda")[None, :] < _lens(lens)[:, None]
 
 
-def _oracle(q, kc, vc, lens, causal, window):
+def _oracle(q, kc, vc, lens, causal, window, softmax_scale=None):
     """(fp32-upcast oracle, low-precision reordered oracle) with the cache lengths as a key mask."""
-    common = dict(key_padding_mask=_key_mask(lens, kc.size(1)), causal=causal, window_size=window)
+    common = dict(key_padding_mask=_key_mask(lens, kc.size(1)), causal=causal, window_size=window,
+                  softmax_scale=softmax_scale)
     return attention_reference(q, kc, vc, **common), attention_reference(q, kc, vc, upcast=False, reorder_ops=True, **common)
 
 
-def _lse2(q, kc, lens, causal, window):
+def _lse2(q, kc, lens, causal, window, softmax_scale=None):
     """Base-2 log-sum-exp of the scaled scores over the same mask: [B, Hq, Sq] fp32, -inf on empty rows."""
     mask = _key_mask(lens, kc.size(1))
     if causal:
         window = (window[0], 0)
     kf = torch.repeat_interleave(kc.float(), q.size(2) // kc.size(2), dim=2)
-    scores = torch.einsum("bqhd,bkhd->bhqk", q.float(), kf) / math.sqrt(q.size(3))
+    scores = torch.einsum("bqhd,bkhd->bhqk", q.float(), kf)
+    scores = scores / math.sqrt(q.size(3)) if softmax_scale is None else scores * softmax_scale
     scores = scores.masked_fill(~mask[:, None, None, :], float("-inf"))
     if window[0] >= 0 or window[1] >= 0:
         scores = scores.masked_fill(window_mask(q.size(1), kc.size(1), window, None, mask, q.device), float("-inf"))
     return torch.logsumexp(scores, dim=-1) * LOG2E
 
 
-def _check(q, kc, vc, lens, out, lse, causal, window):
+def _check(q, kc, vc, lens, out, lse, causal, window, softmax_scale=None):
     """The reference tests' forward rule with no escape taken, and LSE2 by the rule of test_golden."""
-    ref, pt = _oracle(q, kc, vc, lens, causal, window)
+    ref, pt = _oracle(q, kc, vc, lens, causal, window, softmax_scale)
     before = dict(tolerance.ESCAPES)
     report = check_fa_tolerance(q, kc, vc, None, out, ref, pt)
     print({key: f"{val:.3e}" for key, val in report.items()})
     assert tolerance.ESCAPES["ulp"] == before["ulp"] and tolerance.ESCAPES["dv_sum"] == before["dv_sum"], report
     assert out.shape == q.shape and out.dtype == q.dtype and torch.isfinite(out).all()
     if lse is not None:
-        want = _lse2(q, kc, lens, causal, window)
+        want = _lse2(q, kc, lens, causal, window, softmax_scale)
         assert lse.shape == want.shape and lse.dtype == torch.float32
         finite = torch.isfinite(want)
         assert torch.allclose(lse[finite], want[finite], rtol=1e-3, atol=1e-3), (lse[finite] - want[finite]).abs().max()
