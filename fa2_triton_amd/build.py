@@ -32,67 +32,33 @@ def hipcc() -> str:
     raise RuntimeError("hipcc not found (set HIPCC or install ROCm at /opt/rocm)")
 
 
+# The generated units, one per (unit prefix, dtype, tile): (prefix, header, explicit instantiations
+# of the launchers that header defines); {bf} and {dt} are the unit's template arguments.  Each
+# family has units of its own so that none of the others grows.
+UNITS = (
+    ("fwd", "fwd_kernel.h", ("launch_fwd_dt<{bf}, {dt}>(const fa2_fwd_args&, LaunchCtx)",)),
+    ("bwd", "bwd_kernel.h", ("launch_bwd_dt<{bf}, {dt}>(const fa2_bwd_args&, LaunchCtx, int)",)),
+    ("local", "local_kernel.h", ("launch_fwd_local<{bf}, {dt}>(const fa2_fwd_args&, const FwdPlan&, hipStream_t)",
+                                 "launch_bwd_local<{bf}, {dt}>(const fa2_bwd_args&, const BwdPlan&, hipStream_t)")),
+    ("kvcache", "kvcache_kernel.h", ("launch_kvcache_split<{bf}, {dt}>(const fa2_kvcache_args&, int, hipStream_t)",)),
+    ("kvcache_paged", "kvcache_kernel.h",
+     ("launch_kvcache_split<{bf}, {dt}>(const fa2_paged_kvcache_args&, int, hipStream_t)",)),
+)
+
+
 def generated_sources():
     os.makedirs(GEN, exist_ok=True)
     srcs = []
-    for kind in ("fwd", "bwd"):
+    for prefix, header, insts in UNITS:
         for dname, flag in DTYPES.items():
             for dt in TILES:
-                path = os.path.join(GEN, f"{kind}_{dname}_d{dt}.hip")
-                extra = ", int" if kind == "bwd" else ""
-                body = (
-                    f'#include "../{kind}_kernel.h"\n'
-                    f"namespace fa2 {{\n"
-                    f"template hipError_t launch_{kind}_dt<{flag}, {dt}>(const fa2_{kind}_args&, bool{extra}, hipStream_t);\n"
-                    f"}}\n"
-                )
+                path = os.path.join(GEN, f"{prefix}_{dname}_d{dt}.hip")
+                lines = "".join(f"template hipError_t {i.format(bf=flag, dt=dt)};\n" for i in insts)
+                body = f'#include "../{header}"\nnamespace fa2 {{\n{lines}}}\n'
                 if not os.path.exists(path) or open(path).read() != body:
                     with open(path, "w") as f:
                         f.write(body)
                 srcs.append(path)
-    # the sliding-window kernels (local_kernel.h), in units of their own so that none above grows
-    for dname, flag in DTYPES.items():
-        for dt in TILES:
-            path = os.path.join(GEN, f"local_{dname}_d{dt}.hip")
-            body = (
-                '#include "../local_kernel.h"\n'
-                "namespace fa2 {\n"
-                f"template hipError_t launch_fwd_local<{flag}, {dt}>(const fa2_fwd_args&, bool, hipStream_t);\n"
-                f"template hipError_t launch_bwd_local<{flag}, {dt}>(const fa2_bwd_args&, bool, int, hipStream_t);\n"
-                "}\n"
-            )
-            if not os.path.exists(path) or open(path).read() != body:
-                with open(path, "w") as f:
-                    f.write(body)
-            srcs.append(path)
-    # the KV-cache decode kernel (kvcache_kernel.h), again in units of its own
-    for dname, flag in DTYPES.items():
-        for dt in TILES:
-            path = os.path.join(GEN, f"kvcache_{dname}_d{dt}.hip")
-            body = (
-                '#include "../kvcache_kernel.h"\n'
-                "namespace fa2 {\n"
-                f"template hipError_t launch_kvcache_split<{flag}, {dt}>(const fa2_kvcache_args&, int, hipStream_t);\n"
-                "}\n"
-            )
-            if not os.path.exists(path) or open(path).read() != body:
-                with open(path, "w") as f:
-                    f.write(body)
-            srcs.append(path)
-    # its paged variant (kvcache_paged_kernel.h)
-    for dname, flag in DTYPES.items():
-        for dt in TILES:
-            path = os.path.join(GEN, f"kvcache_paged_{dname}_d{dt}.hip")
-            body = (
-                '#include "../kvcache_paged_kernel.h"\n'
-                "namespace fa2 {\n"
-                f"template hipError_t launch_kvcache_paged_split<{flag}, {dt}>(const fa2_paged_kvcache_args&, int, hipStream_t);\n"
-                "}\n"
-            )
-            if not os.path.exists(path) or open(path).read() != body:
-                with open(path, "w") as f:
-                    f.write(body)
-            srcs.append(path)
     return srcs
 
 

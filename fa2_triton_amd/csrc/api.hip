@@ -7,7 +7,6 @@
 #include <stdio.h>
 
 #include "fa2_internal.h"
-#include "kvcache_host.h"
 #if FA2_HP_STAMPS
 #include "common.h"
 #endif
@@ -15,6 +14,16 @@
 namespace {
 
 thread_local char g_err[512] = "";
+
+// Every launching entry point takes the address of the error string, the library's one
+// thread-local.  Built as this library is (-fPIC, shared, general-dynamic TLS without descriptors)
+// that is a __tls_get_addr call, which the empty asm keeps alive; under another TLS model the line
+// compiles to nothing.  With glibc older than 2.39 (BZ 19924) every __tls_get_addr of a thread, the
+// HIP runtime's and the caller's too, takes the slow path from the dlopen of a module with
+// thread-locals until the thread has looked up those of the newest one, usually this library.
+// Measured with glibc 2.35, decode at (B, L) = (1, 8192), event time per synchronous call in fresh
+// processes: 47.8 / 47.9 / 48.3 us without this lookup, 45.6 / 45.7 / 45.6 us with it.
+inline void touch_thread_state() { asm volatile("" ::"r"(&g_err[0])); }
 
 int fail(int code, const char* fmt, ...) {
   va_list ap;
@@ -24,18 +33,12 @@ int fail(int code, const char* fmt, ...) {
   return code;
 }
 
-int hip_status(hipError_t e, const char* what) {
+int hip_status(hipError_t e, const char* entry, const char* what) {
   if (e == hipSuccess) return FA2_OK;
-  return fail(FA2_E_HIP, "%s: %s", what, hipGetErrorString(e));
+  return fail(FA2_E_HIP, "%s %s: %s", entry, what, hipGetErrorString(e));
 }
 
-int pick_dt(int d) {
-  if (d <= 32) return 32;
-  if (d <= 64) return 64;
-  if (d <= 128) return 128;
-  if (d <= 256) return 256;
-  return 0;
-}
+using fa2::head_dim_tile;
 
 bool aligned16(const void* ptr) { return ((uintptr_t)ptr & 15) == 0; }
 bool strides8(const int64_t* s) { return s[0] % 8 == 0 && s[1] % 8 == 0 && s[2] % 8 == 0; }
@@ -49,7 +52,7 @@ int check_common(int B, int Hq, int Hkv, int Sq, int Sk, int D, int dtype, int l
     return fail(FA2_E_INVALID, "bad sizes B=%d Hq=%d Hkv=%d Sq=%d Sk=%d D=%d", B, Hq, Hkv, Sq, Sk, D);
   if (Hq % Hkv != 0) return fail(FA2_E_INVALID, "heads_q=%d is not divisible by heads_kv=%d", Hq, Hkv);
   if (dtype != FA2_F16 && dtype != FA2_BF16) return fail(FA2_E_INVALID, "dtype %d: only fp16 and bf16", dtype);
-  if (!pick_dt(D)) return fail(FA2_E_UNSUPPORTED, "head_dim %d > 256", D);
+  if (!head_dim_tile(D)) return fail(FA2_E_UNSUPPORTED, "head_dim %d > 256", D);
   if (lse_rs < ((Sq + 31) / 32) * 32 || lse_rs % 32 != 0)
     return fail(FA2_E_INVALID, "lse_row_stride %d must be a multiple of 32 and >= seqlen_q rounded up (%d)", lse_rs, Sq);
   if (cu && Sq != Sk) return fail(FA2_E_INVALID, "varlen (cu_seqlens) requires seqlen_q == seqlen_k");
@@ -90,7 +93,7 @@ int kvcache_check_sizes(const fa2_kvcache_args* a) {
   if (a->heads_q % a->heads_kv != 0)
     return fail(FA2_E_INVALID, "heads_q=%d is not divisible by heads_kv=%d", a->heads_q, a->heads_kv);
   if (a->dtype != FA2_F16 && a->dtype != FA2_BF16) return fail(FA2_E_INVALID, "dtype %d: only fp16 and bf16", a->dtype);
-  if (!pick_dt(a->head_dim)) return fail(FA2_E_UNSUPPORTED, "head_dim %d > 256", a->head_dim);
+  if (!head_dim_tile(a->head_dim)) return fail(FA2_E_UNSUPPORTED, "head_dim %d > 256", a->head_dim);
   if (a->capacity > (1 << 30) || a->seqlen_q > (1 << 24))
     return fail(FA2_E_UNSUPPORTED, "capacity %d > 2^30 or seqlen_q %d > 2^24", a->capacity, a->seqlen_q);
   if (a->num_splits < 0 || a->num_splits > FA2_KVCACHE_MAX_SPLITS)
@@ -98,35 +101,67 @@ int kvcache_check_sizes(const fa2_kvcache_args* a) {
   return FA2_OK;
 }
 
-template <typename F4, typename F8, typename F12, typename F16>
-hipError_t dispatch_dt(int dt, F4 f32, F8 f64, F12 f128, F16 f256) {
-  switch (dt) {
-    case 32: return f32();
-    case 64: return f64();
-    case 128: return f128();
-    default: return f256();
-  }
-}
-
-}  // namespace
-
-namespace fa2 {
-// the policy of the fa2_*_ex call running on this thread (nullptr: defaults); set only for the
-// duration of that call (PolicyScope), so the library keeps no state between calls
-thread_local const fa2_policy* g_call_policy = nullptr;
-}  // namespace fa2
-
-namespace {
-struct PolicyScope {
-  const fa2_policy* prev;
-  explicit PolicyScope(const fa2_policy* p) : prev(fa2::g_call_policy) { fa2::g_call_policy = p; }
-  ~PolicyScope() { fa2::g_call_policy = prev; }
-};
 int check_policy(const fa2_policy* p) {
   if (!p) return FA2_OK;
   if (p->disable & ~(uint32_t)(FA2_PATH_FWD_HP | FA2_PATH_DQ_HP | FA2_PATH_DKDV_HP))
     return fail(FA2_E_INVALID, "unknown path bits 0x%x", p->disable);
   if (p->grid_cap < 0) return fail(FA2_E_INVALID, "grid_cap %d < 0", p->grid_cap);
+  return FA2_OK;
+}
+
+// Everything fa2_fwd_kvcache checks after the sizes, shared with the paged call (whose pools are
+// k_cache / v_cache with block, row and head strides): pointers, the new rows, 16-byte rows, the
+// workspace and the grid.  On success *nsplit_out is the split count of the call.
+int kvcache_check_call(const fa2_kvcache_args* a, int* nsplit_out) {
+  if (!a->q || !a->k_cache || !a->v_cache || !a->o) return fail(FA2_E_INVALID, "null tensor pointer");
+  if ((a->k_new != nullptr) != (a->v_new != nullptr)) return fail(FA2_E_INVALID, "k_new and v_new must be given together");
+  if (a->k_new ? a->seqlen_new < 1 : a->seqlen_new != 0)
+    return fail(FA2_E_INVALID, "seqlen_new=%d %s k_new / v_new", a->seqlen_new, a->k_new ? "with" : "without");
+  const int D = a->head_dim;
+  if (D % 8 != 0) return fail(FA2_E_UNSUPPORTED, "head_dim %d is not a multiple of 8 (16-byte rows)", D);
+  bool aligned = vec_ok(D, a->q, a->q_stride) && vec_ok(D, a->k_cache, a->k_cache_stride) &&
+                 vec_ok(D, a->v_cache, a->v_cache_stride) && vec_ok(D, a->o, a->o_stride);
+  if (a->k_new) aligned = aligned && vec_ok(D, a->k_new, a->k_new_stride) && vec_ok(D, a->v_new, a->v_new_stride);
+  if (!aligned) return fail(FA2_E_UNSUPPORTED, "a tensor's rows are not 16-byte aligned (pointer or strides)");
+  const int nsplit = fa2_kvcache_num_splits(a);
+  const int64_t need = fa2::kv_workspace_bytes(*a, nsplit);
+  if (need > 0) {
+    if (!a->workspace || a->workspace_bytes < need)
+      return fail(FA2_E_INVALID, "workspace_bytes %lld < %lld required for %d splits",
+                  (long long)(a->workspace ? a->workspace_bytes : 0), (long long)need, nsplit);
+    if (!aligned16(a->workspace)) return fail(FA2_E_INVALID, "workspace must be 16-byte aligned");
+  }
+  if (fa2::kv_units(*a) * nsplit > 0x7FFFFFFFll) return fail(FA2_E_UNSUPPORTED, "grid of %lld units x %d splits", (long long)fa2::kv_units(*a), nsplit);
+  *nsplit_out = nsplit;
+  return FA2_OK;
+}
+
+// A call of either layout (Args = fa2_kvcache_args or fa2_paged_kvcache_args, its sizes checked):
+// the shared checks, then the append, the split kernel and the combination.
+template <typename Args>
+int run_kvcache(const Args& args, const char* entry, void* stream) {
+  const fa2_kvcache_args& a = fa2::kv_base(args);
+  int nsplit = 1;
+  if (int rc = kvcache_check_call(&a, &nsplit)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  if (a.k_new)
+    if (int rc = hip_status(fa2::launch_kvcache_append(args, st), entry, "append launch")) return rc;
+  const hipError_t e = fa2::dispatch([&](auto bf, auto dt) { return fa2::launch_kvcache_split<bf.value, dt.value>(args, nsplit, st); },
+                                     a.dtype == FA2_BF16, fa2::dtypes{}, head_dim_tile(a.head_dim), fa2::tiles{});
+  if (int rc = hip_status(e, entry, "launch")) return rc;
+  if (nsplit > 1) return hip_status(fa2::launch_kvcache_combine(a, nsplit, st), entry, "combine launch");
+  return FA2_OK;
+}
+
+// The sizes of a paged call: kvcache_check_sizes on the base, then the page size and the table
+// geometry (max_blocks is capacity / page_block_size).
+int paged_kvcache_check_sizes(const fa2_paged_kvcache_args* a) {
+  if (int rc = kvcache_check_sizes(&a->base)) return rc;
+  const int P = a->page_block_size;
+  if (P < 16 || (P & (P - 1)) != 0) return fail(FA2_E_INVALID, "page_block_size=%d must be a power of two >= 16", P);
+  if (a->num_blocks < 1) return fail(FA2_E_INVALID, "num_blocks=%d must be >= 1", a->num_blocks);
+  if (a->base.capacity % P != 0)
+    return fail(FA2_E_INVALID, "capacity=%d must be max_blocks * page_block_size (a multiple of %d)", a->base.capacity, P);
   return FA2_OK;
 }
 }  // namespace
@@ -140,9 +175,9 @@ const char* fa2_last_error(void) { return g_err; }
 int fa2_fwd(const fa2_fwd_args* a, void* stream) { return fa2_fwd_ex(a, nullptr, stream); }
 
 int fa2_fwd_ex(const fa2_fwd_args* a, const fa2_policy* policy, void* stream) {
+  touch_thread_state();
   if (!a) return fail(FA2_E_INVALID, "null args");
   if (int prc = check_policy(policy)) return prc;
-  PolicyScope scope(policy);
   int rc = check_common(a->batch, a->heads_q, a->heads_kv, a->seqlen_q, a->seqlen_k, a->head_dim, a->dtype,
                         a->lse_row_stride, a->cu_seqlens, a->dropout_p);
   if (rc) return rc;
@@ -161,29 +196,18 @@ int fa2_fwd_ex(const fa2_fwd_args* a, const fa2_policy* policy, void* stream) {
   const int D = a->head_dim;
   const bool aligned = vec_ok(D, a->q, a->q_stride) && vec_ok(D, a->k, a->k_stride) &&
                        vec_ok(D, a->v, a->v_stride) && vec_ok(D, a->o, a->o_stride);
-  hipStream_t st = (hipStream_t)stream;
-  const bool bf = a->dtype == FA2_BF16;
-  const int dt = pick_dt(D);
-  hipError_t e;
-  if (bf)
-    e = dispatch_dt(dt, [&] { return fa2::launch_fwd_dt<true, 32>(*a, aligned, st); },
-                    [&] { return fa2::launch_fwd_dt<true, 64>(*a, aligned, st); },
-                    [&] { return fa2::launch_fwd_dt<true, 128>(*a, aligned, st); },
-                    [&] { return fa2::launch_fwd_dt<true, 256>(*a, aligned, st); });
-  else
-    e = dispatch_dt(dt, [&] { return fa2::launch_fwd_dt<false, 32>(*a, aligned, st); },
-                    [&] { return fa2::launch_fwd_dt<false, 64>(*a, aligned, st); },
-                    [&] { return fa2::launch_fwd_dt<false, 128>(*a, aligned, st); },
-                    [&] { return fa2::launch_fwd_dt<false, 256>(*a, aligned, st); });
-  return hip_status(e, "fa2_fwd launch");
+  const fa2::LaunchCtx ctx = {(hipStream_t)stream, aligned, policy};
+  const hipError_t e = fa2::dispatch([&](auto bf, auto dt) { return fa2::launch_fwd_dt<bf.value, dt.value>(*a, ctx); },
+                                     a->dtype == FA2_BF16, fa2::dtypes{}, head_dim_tile(D), fa2::tiles{});
+  return hip_status(e, "fa2_fwd", "launch");
 }
 
 int fa2_bwd_stages(const fa2_bwd_args* a, int stages, void* stream) { return fa2_bwd_stages_ex(a, stages, nullptr, stream); }
 
 int fa2_bwd_stages_ex(const fa2_bwd_args* a, int stages, const fa2_policy* policy, void* stream) {
+  touch_thread_state();
   if (!a) return fail(FA2_E_INVALID, "null args");
   if (int prc = check_policy(policy)) return prc;
-  PolicyScope scope(policy);
   int rc = check_common(a->batch, a->heads_q, a->heads_kv, a->seqlen_q, a->seqlen_k, a->head_dim, a->dtype,
                         a->lse_row_stride, a->cu_seqlens, a->dropout_p);
   if (rc) return rc;
@@ -219,21 +243,10 @@ int fa2_bwd_stages_ex(const fa2_bwd_args* a, int stages, const fa2_policy* polic
       return fail(FA2_E_INVALID, "dkv_workspace_bytes %lld < %lld required", (long long)a->dkv_workspace_bytes, (long long)need);
     if (!aligned16(a->dkv_workspace)) return fail(FA2_E_INVALID, "dkv_workspace must be 16-byte aligned");
   }
-  hipStream_t st = (hipStream_t)stream;
-  const bool bf = a->dtype == FA2_BF16;
-  const int dt = pick_dt(D);
-  hipError_t e;
-  if (bf)
-    e = dispatch_dt(dt, [&] { return fa2::launch_bwd_dt<true, 32>(*a, aligned, stages, st); },
-                    [&] { return fa2::launch_bwd_dt<true, 64>(*a, aligned, stages, st); },
-                    [&] { return fa2::launch_bwd_dt<true, 128>(*a, aligned, stages, st); },
-                    [&] { return fa2::launch_bwd_dt<true, 256>(*a, aligned, stages, st); });
-  else
-    e = dispatch_dt(dt, [&] { return fa2::launch_bwd_dt<false, 32>(*a, aligned, stages, st); },
-                    [&] { return fa2::launch_bwd_dt<false, 64>(*a, aligned, stages, st); },
-                    [&] { return fa2::launch_bwd_dt<false, 128>(*a, aligned, stages, st); },
-                    [&] { return fa2::launch_bwd_dt<false, 256>(*a, aligned, stages, st); });
-  return hip_status(e, "fa2_bwd launch");
+  const fa2::LaunchCtx ctx = {(hipStream_t)stream, aligned, policy};
+  const hipError_t e = fa2::dispatch([&](auto bf, auto dt) { return fa2::launch_bwd_dt<bf.value, dt.value>(*a, ctx, stages); },
+                                     a->dtype == FA2_BF16, fa2::dtypes{}, head_dim_tile(D), fa2::tiles{});
+  return hip_status(e, "fa2_bwd", "launch");
 }
 
 int fa2_bwd(const fa2_bwd_args* a, void* stream) { return fa2_bwd_stages(a, a && a->dbias ? 14 : 6, stream); }
@@ -254,7 +267,7 @@ int fa2_cu_seqlens_from_mask(const uint8_t* mask, int64_t mask_row_stride, int32
                              int32_t* cu_seqlens, void* stream) {
   if (!mask || !cu_seqlens || batch < 1 || seqlen < 0) return fail(FA2_E_INVALID, "bad cu_seqlens arguments");
   return hip_status(fa2::launch_cu_seqlens(mask, mask_row_stride, batch, seqlen, cu_seqlens, (hipStream_t)stream),
-                    "fa2_cu_seqlens_from_mask launch");
+                    "fa2_cu_seqlens_from_mask", "launch");
 }
 
 int fa2_abi_minor(void) { return FA2_ABI_MINOR; }
@@ -262,7 +275,7 @@ int fa2_abi_minor(void) { return FA2_ABI_MINOR; }
 int fa2_kvcache_num_splits(const fa2_kvcache_args* a) {
   if (!a || kvcache_check_sizes(a)) return 1;
   if (a->num_splits >= 1) return a->num_splits;
-  return fa2::kv_auto_splits(*a, fa2::kv_cu_count());
+  return fa2::kv_auto_splits(*a, fa2::device_cu_count());
 }
 
 int64_t fa2_kvcache_workspace_bytes(const fa2_kvcache_args* a) {
@@ -270,69 +283,11 @@ int64_t fa2_kvcache_workspace_bytes(const fa2_kvcache_args* a) {
   return fa2::kv_workspace_bytes(*a, fa2_kvcache_num_splits(a));
 }
 
-// Everything fa2_fwd_kvcache checks after the sizes, shared with the paged call (whose pools are
-// k_cache / v_cache with block, row and head strides): pointers, the new rows, 16-byte rows, the
-// workspace and the grid.  On success *nsplit_out is the split count of the call.
-static int kvcache_check_call(const fa2_kvcache_args* a, int* nsplit_out) {
-  if (!a->q || !a->k_cache || !a->v_cache || !a->o) return fail(FA2_E_INVALID, "null tensor pointer");
-  if ((a->k_new != nullptr) != (a->v_new != nullptr)) return fail(FA2_E_INVALID, "k_new and v_new must be given together");
-  if (a->k_new ? a->seqlen_new < 1 : a->seqlen_new != 0)
-    return fail(FA2_E_INVALID, "seqlen_new=%d %s k_new / v_new", a->seqlen_new, a->k_new ? "with" : "without");
-  const int D = a->head_dim;
-  if (D % 8 != 0) return fail(FA2_E_UNSUPPORTED, "head_dim %d is not a multiple of 8 (16-byte rows)", D);
-  bool aligned = vec_ok(D, a->q, a->q_stride) && vec_ok(D, a->k_cache, a->k_cache_stride) &&
-                 vec_ok(D, a->v_cache, a->v_cache_stride) && vec_ok(D, a->o, a->o_stride);
-  if (a->k_new) aligned = aligned && vec_ok(D, a->k_new, a->k_new_stride) && vec_ok(D, a->v_new, a->v_new_stride);
-  if (!aligned) return fail(FA2_E_UNSUPPORTED, "a tensor's rows are not 16-byte aligned (pointer or strides)");
-  const int nsplit = fa2_kvcache_num_splits(a);
-  const int64_t need = fa2::kv_workspace_bytes(*a, nsplit);
-  if (need > 0) {
-    if (!a->workspace || a->workspace_bytes < need)
-      return fail(FA2_E_INVALID, "workspace_bytes %lld < %lld required for %d splits",
-                  (long long)(a->workspace ? a->workspace_bytes : 0), (long long)need, nsplit);
-    if (!aligned16(a->workspace)) return fail(FA2_E_INVALID, "workspace must be 16-byte aligned");
-  }
-  if (fa2::kv_units(*a) * nsplit > 0x7FFFFFFFll) return fail(FA2_E_UNSUPPORTED, "grid of %lld units x %d splits", (long long)fa2::kv_units(*a), nsplit);
-  *nsplit_out = nsplit;
-  return FA2_OK;
-}
-
 int fa2_fwd_kvcache(const fa2_kvcache_args* a, void* stream) {
+  touch_thread_state();
   if (!a) return fail(FA2_E_INVALID, "null args");
   if (int rc = kvcache_check_sizes(a)) return rc;
-  int nsplit = 1;
-  if (int rc = kvcache_check_call(a, &nsplit)) return rc;
-  const int D = a->head_dim;
-  hipStream_t st = (hipStream_t)stream;
-  if (a->k_new)
-    if (int rc = hip_status(fa2::launch_kvcache_append(*a, st), "fa2_fwd_kvcache append launch")) return rc;
-  const bool bf = a->dtype == FA2_BF16;
-  hipError_t e;
-  if (bf)
-    e = dispatch_dt(pick_dt(D), [&] { return fa2::launch_kvcache_split<true, 32>(*a, nsplit, st); },
-                    [&] { return fa2::launch_kvcache_split<true, 64>(*a, nsplit, st); },
-                    [&] { return fa2::launch_kvcache_split<true, 128>(*a, nsplit, st); },
-                    [&] { return fa2::launch_kvcache_split<true, 256>(*a, nsplit, st); });
-  else
-    e = dispatch_dt(pick_dt(D), [&] { return fa2::launch_kvcache_split<false, 32>(*a, nsplit, st); },
-                    [&] { return fa2::launch_kvcache_split<false, 64>(*a, nsplit, st); },
-                    [&] { return fa2::launch_kvcache_split<false, 128>(*a, nsplit, st); },
-                    [&] { return fa2::launch_kvcache_split<false, 256>(*a, nsplit, st); });
-  if (int rc = hip_status(e, "fa2_fwd_kvcache launch")) return rc;
-  if (nsplit > 1) return hip_status(fa2::launch_kvcache_combine(*a, nsplit, st), "fa2_fwd_kvcache combine launch");
-  return FA2_OK;
-}
-
-// The sizes of a paged call: kvcache_check_sizes on the base, then the page size and the table
-// geometry (max_blocks is capacity / page_block_size).
-static int paged_kvcache_check_sizes(const fa2_paged_kvcache_args* a) {
-  if (int rc = kvcache_check_sizes(&a->base)) return rc;
-  const int P = a->page_block_size;
-  if (P < 16 || (P & (P - 1)) != 0) return fail(FA2_E_INVALID, "page_block_size=%d must be a power of two >= 16", P);
-  if (a->num_blocks < 1) return fail(FA2_E_INVALID, "num_blocks=%d must be >= 1", a->num_blocks);
-  if (a->base.capacity % P != 0)
-    return fail(FA2_E_INVALID, "capacity=%d must be max_blocks * page_block_size (a multiple of %d)", a->base.capacity, P);
-  return FA2_OK;
+  return run_kvcache(*a, "fa2_fwd_kvcache", stream);
 }
 
 int fa2_paged_kvcache_num_splits(const fa2_paged_kvcache_args* a) {
@@ -346,6 +301,7 @@ int64_t fa2_paged_kvcache_workspace_bytes(const fa2_paged_kvcache_args* a) {
 }
 
 int fa2_fwd_kvcache_paged(const fa2_paged_kvcache_args* a, void* stream) {
+  touch_thread_state();
   if (!a) return fail(FA2_E_INVALID, "null args");
   if (int rc = paged_kvcache_check_sizes(a)) return rc;
   if (!a->block_table) return fail(FA2_E_INVALID, "null block_table");
@@ -353,28 +309,7 @@ int fa2_fwd_kvcache_paged(const fa2_paged_kvcache_args* a, void* stream) {
   if (a->block_table_stride < max_blocks)
     return fail(FA2_E_INVALID, "block_table_stride %lld < max_blocks %lld (capacity / page_block_size)",
                 (long long)a->block_table_stride, (long long)max_blocks);
-  int nsplit = 1;
-  if (int rc = kvcache_check_call(&a->base, &nsplit)) return rc;
-  const int D = a->base.head_dim;
-  hipStream_t st = (hipStream_t)stream;
-  if (a->base.k_new)
-    if (int rc = hip_status(fa2::launch_kvcache_paged_append(*a, st), "fa2_fwd_kvcache_paged append launch")) return rc;
-  const bool bf = a->base.dtype == FA2_BF16;
-  hipError_t e;
-  if (bf)
-    e = dispatch_dt(pick_dt(D), [&] { return fa2::launch_kvcache_paged_split<true, 32>(*a, nsplit, st); },
-                    [&] { return fa2::launch_kvcache_paged_split<true, 64>(*a, nsplit, st); },
-                    [&] { return fa2::launch_kvcache_paged_split<true, 128>(*a, nsplit, st); },
-                    [&] { return fa2::launch_kvcache_paged_split<true, 256>(*a, nsplit, st); });
-  else
-    e = dispatch_dt(pick_dt(D), [&] { return fa2::launch_kvcache_paged_split<false, 32>(*a, nsplit, st); },
-                    [&] { return fa2::launch_kvcache_paged_split<false, 64>(*a, nsplit, st); },
-                    [&] { return fa2::launch_kvcache_paged_split<false, 128>(*a, nsplit, st); },
-                    [&] { return fa2::launch_kvcache_paged_split<false, 256>(*a, nsplit, st); });
-  if (int rc = hip_status(e, "fa2_fwd_kvcache_paged launch")) return rc;
-  if (nsplit > 1)
-    return hip_status(fa2::launch_kvcache_combine(a->base, nsplit, st), "fa2_fwd_kvcache_paged combine launch");
-  return FA2_OK;
+  return run_kvcache(*a, "fa2_fwd_kvcache_paged", stream);
 }
 
 #if FA2_HP_STAMPS

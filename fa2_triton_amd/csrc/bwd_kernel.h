@@ -561,112 +561,81 @@ __global__ void __launch_bounds__(256, DT <= 64 && !DROPOUT ? 2 : 1) dbias_kerne
 }
 
 // ---------------------------------------------------------------------------------------------
-template <bool BF16>
-static void launch_dkv_reduce(const fa2_bwd_args& a, int nsplit, hipStream_t st) {
-  if (nsplit <= 1) return;
-  const int64_t n = (int64_t)a.batch * a.heads_kv * a.seqlen_k * ((a.head_dim + 3) / 4);
-  hipLaunchKernelGGL((dkv_reduce_kernel<BF16>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a, nsplit);
+// the standalone delta launch, shared with the windowed backward (local_kernel.h)
+template <bool BF16, bool ALIGNED>
+static void launch_delta(const fa2_bwd_args& a, hipStream_t st) {
+  dim3 grid((a.lse_row_stride + 15) / 16, a.batch * a.heads_q);
+  hipLaunchKernelGGL((delta_kernel<BF16, ALIGNED>), grid, dim3(256), 0, st, a);
 }
 
-template <bool BF16, int DT, bool CAUSAL, bool BIAS, bool DROPOUT, bool ALIGNED>
-static hipError_t launch_bwd_t(const fa2_bwd_args& a, int stages, hipStream_t st) {
-  // order: standalone delta (bit 0), dQ (bit 2; also writes delta), then dK/dV (bit 1, reads it)
-  // zero-sized problems launch nothing for that side: Sk == 0 -> dQ = 0 (dq_kernel sees no key
-  // tile and writes zeros), no dK/dV rows; Sq == 0 -> dK/dV = 0 (dkdv_kernel sees no query
-  // tile and writes zeros), no dQ rows
-  if ((stages & 1) && a.lse_row_stride > 0) {
-    dim3 grid((a.lse_row_stride + 15) / 16, a.batch * a.heads_q);
-    hipLaunchKernelGGL((delta_kernel<BF16, ALIGNED>), grid, dim3(256), 0, st, a);
-  }
-  if ((stages & 4) && a.seqlen_q > 0) {
-    if constexpr (DT == 128 && !BIAS && ALIGNED) {
-      // hand-placed one-wave-per-SIMD dQ (dq_hp_kernel.h) for D = 128 exactly (dropout: with
-      // the forward's saved keep words)
-      if (dq_hp_ok(a, true)) {
-        launch_dq_hp<BF16, CAUSAL, DROPOUT>(a, st);
-        goto dq_done;
+// The stages of a plan (select_bwd) that is not local, in the plan's order: standalone delta (bit
+// 0), dQ (bit 2; also writes delta), the bias gradient (bit 3), dK/dV (bit 1, reads delta).  What
+// no plan holds is ruled out here: BIASK 16 / 17 (LDS-staged bias tiles) exist only with aligned
+// rows, the hand-placed kernels only at DT == 128 && BIASK == 0 && ALIGNED (D = 128 exactly;
+// dropout: with the forward's saved keep words).
+template <bool BF16, int DT, bool CAUSAL, int BIASK, bool DROPOUT, bool ALIGNED>
+static hipError_t launch_bwd_t(const fa2_bwd_args& a, const BwdPlan& p, LaunchCtx ctx) {
+  if constexpr (BIASK >= 16 && !ALIGNED) {
+    return hipErrorInvalidValue;
+  } else {
+    constexpr bool HP = DT == 128 && BIASK == 0 && ALIGNED;
+    hipStream_t st = ctx.stream;
+    for (int i = 0; i < p.nstages; ++i)
+      if (p.stage[i].path == Path::hand_placed && !HP) return hipErrorInvalidValue;
+    for (int i = 0; i < p.nstages; ++i) {
+      const bool hp = p.stage[i].path == Path::hand_placed;
+      switch (p.stage[i].kind) {
+        case Stage::delta: launch_delta<BF16, ALIGNED>(a, st); break;
+        case Stage::dq:
+          if (hp) {
+            if constexpr (HP) launch_dq_hp<BF16, CAUSAL, DROPOUT>(a, ctx);
+          } else {
+            constexpr int NW = DqCfg<DT>::NW, BM = NW * 32;
+            const int nmb = (a.seqlen_q + BM - 1) / BM;
+            dim3 grid((CAUSAL ? (nmb + 1) / 2 : nmb) * a.batch * a.heads_q);  // causal: mirrored pairs of blocks
+            dispatch(  // dQ in fp32 concerns this launch alone
+                [&](auto f32) {
+                  hipLaunchKernelGGL((dq_kernel<BF16, DT, CAUSAL, BIASK, DROPOUT, ALIGNED, f32.value>), grid, dim3(NW * 64), 0, st, a);
+                  return hipSuccess;
+                },
+                p.dq_f32, bools{});
+          }
+          break;
+        case Stage::dbias: {
+          const int bb = a.bias_stride[0] != 0 ? a.batch : 1, hb = a.bias_stride[1] != 0 ? a.heads_q : 1;
+          const int nkc = ((a.seqlen_k + 63) / 64 + kDbiasChunk - 1) / kDbiasChunk;
+          dim3 grid(dbias_blocks((a.seqlen_q + 127) / 128, nkc), bb * hb);
+          hipLaunchKernelGGL((dbias_kernel<BF16, DT, CAUSAL, DROPOUT, ALIGNED>), grid, dim3(256), 0, st, a);
+          break;
+        }
+        case Stage::dkdv:
+          if (hp) {
+            if constexpr (HP) launch_dkdv_hp<BF16, CAUSAL, DROPOUT>(a, p.nsplit, ctx);
+          } else {
+            dim3 grid(((a.seqlen_k + 127) / 128) * a.batch * a.heads_kv * p.nsplit);
+            hipLaunchKernelGGL((dkdv_kernel<BF16, DT, CAUSAL, BIASK, DROPOUT, ALIGNED>), grid, dim3(256), 0, st, a, p.nsplit);
+          }
+          if (p.reduce) {
+            const int64_t n = (int64_t)a.batch * a.heads_kv * a.seqlen_k * ((a.head_dim + 3) / 4);
+            hipLaunchKernelGGL((dkv_reduce_kernel<BF16>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a, p.nsplit);
+          }
+          break;
       }
     }
-    {
-    constexpr int NW = DqCfg<DT>::NW, BM = NW * 32;
-    constexpr bool PAIR = CAUSAL;
-    const int nmb = (a.seqlen_q + BM - 1) / BM;
-    dim3 grid((PAIR ? (nmb + 1) / 2 : nmb) * a.batch * a.heads_q);
-    auto dq = [&](auto biask_c) {
-      constexpr int BK = decltype(biask_c)::value;
-      if (a.dq_dtype == FA2_F32)
-        hipLaunchKernelGGL((dq_kernel<BF16, DT, CAUSAL, BK, DROPOUT, ALIGNED, true>), grid, dim3(NW * 64), 0, st, a);
-      else
-        hipLaunchKernelGGL((dq_kernel<BF16, DT, CAUSAL, BK, DROPOUT, ALIGNED, false>), grid, dim3(NW * 64), 0, st, a);
-    };
-    if constexpr (!BIAS) {
-      dq(std::integral_constant<int, 0>{});
-    } else if constexpr (ALIGNED) {
-      // a 16-bit bias with 16-byte aligned rows: LDS-staged bias tiles
-      if (bias16_rows(a.bias, a.bias_dtype, a.bias_stride))
-        a.bias_dtype == FA2_BF16 ? dq(std::integral_constant<int, 17>{}) : dq(std::integral_constant<int, 16>{});
-      else
-        dq(std::integral_constant<int, 1>{});
-    } else {
-      dq(std::integral_constant<int, 1>{});
-    }
-    }
+    return hipGetLastError();
   }
-dq_done:
-  if ((stages & 8) && BIAS && a.dbias && a.seqlen_q > 0 && a.seqlen_k > 0) {
-    const int bb = a.bias_stride[0] != 0 ? a.batch : 1, hb = a.bias_stride[1] != 0 ? a.heads_q : 1;
-    const int nkc = ((a.seqlen_k + 63) / 64 + kDbiasChunk - 1) / kDbiasChunk;
-    dim3 grid(dbias_blocks((a.seqlen_q + 127) / 128, nkc), bb * hb);
-    hipLaunchKernelGGL((dbias_kernel<BF16, DT, CAUSAL, DROPOUT, ALIGNED>), grid, dim3(256), 0, st, a);
-  }
-  if ((stages & 2) && a.seqlen_k > 0) {
-    const int ns = dkv_split(a);
-    if constexpr (DT == 128 && !BIAS && ALIGNED) {
-      // hand-placed one-wave-per-SIMD dK/dV (dkdv_hp_kernel.h) for D = 128 exactly (dropout: with
-      // the forward's saved keep words)
-      if (dkdv_hp_ok(a, true)) {
-        launch_dkdv_hp<BF16, CAUSAL, DROPOUT>(a, ns, st);
-        launch_dkv_reduce<BF16>(a, ns, st);
-        return hipGetLastError();
-      }
-    }
-    dim3 grid(((a.seqlen_k + 127) / 128) * a.batch * a.heads_kv * ns);
-    auto dkdv = [&](auto biask_c) {
-      constexpr int BK = decltype(biask_c)::value;
-      hipLaunchKernelGGL((dkdv_kernel<BF16, DT, CAUSAL, BK, DROPOUT, ALIGNED>), grid, dim3(256), 0, st, a, ns);
-    };
-    if constexpr (!BIAS) {
-      dkdv(std::integral_constant<int, 0>{});
-    } else if constexpr (ALIGNED) {
-      if (bias16_rows(a.bias, a.bias_dtype, a.bias_stride))
-        a.bias_dtype == FA2_BF16 ? dkdv(std::integral_constant<int, 17>{}) : dkdv(std::integral_constant<int, 16>{});
-      else
-        dkdv(std::integral_constant<int, 1>{});
-    } else {
-      dkdv(std::integral_constant<int, 1>{});
-    }
-    launch_dkv_reduce<BF16>(a, ns, st);
-  }
-  return hipGetLastError();
 }
 
 template <bool BF16, int DT>
-hipError_t launch_bwd_dt(const fa2_bwd_args& a, bool aligned, int stages, hipStream_t st) {
-  const bool c = a.causal != 0, bi = a.bias != nullptr, dr = a.dropout_p > 0.f;
+hipError_t launch_bwd_dt(const fa2_bwd_args& a, LaunchCtx ctx, int stages) {
+  const BwdPlan p = select_bwd(a, ctx.aligned, stages, ctx.policy);
   // a sliding window (normalised by api.hip) comes first: no other kernel knows one
-  if (a.local) return launch_bwd_local<BF16, DT>(a, aligned, stages, st);
-#define FA2_BWD_CASE(C, B, R, A) \
-  if (c == C && bi == B && dr == R && aligned == A) return launch_bwd_t<BF16, DT, C, B, R, A>(a, stages, st);
-#define FA2_BWD_A(C, B, R) FA2_BWD_CASE(C, B, R, true) FA2_BWD_CASE(C, B, R, false)
-#define FA2_BWD_R(C, B) FA2_BWD_A(C, B, true) FA2_BWD_A(C, B, false)
-  FA2_BWD_R(true, true)
-  FA2_BWD_R(true, false)
-  FA2_BWD_R(false, true)
-  FA2_BWD_R(false, false)
-#undef FA2_BWD_R
-#undef FA2_BWD_A
-#undef FA2_BWD_CASE
-  return hipErrorInvalidValue;
+  if (a.local) return launch_bwd_local<BF16, DT>(a, p, ctx.stream);
+  return dispatch(
+      [&](auto causal, auto biask, auto dropout, auto aligned) {
+        return launch_bwd_t<BF16, DT, causal.value, biask.value, dropout.value, aligned.value>(a, p, ctx);
+      },
+      p.causal, bools{}, p.biask, values<0, 1, 16, 17>{}, p.dropout, bools{}, p.aligned, bools{});
 }
 
 }  // namespace fa2

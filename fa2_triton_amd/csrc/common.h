@@ -102,11 +102,6 @@ FA2_DEV float bias_elem(u32x2 bv, int j) {  // element j (0..3) of a 4-key group
   else return (float)__builtin_bit_cast(_Float16, (uint16_t)((j & 1) ? (wd >> 16) : (wd & 0xFFFFu)));
 }
 constexpr int kBiasTile = 32 * 64 * 2;  // bytes of one wave's bias tile
-// host side: a bias the LDS-staged paths take (16-bit, every row 16-byte aligned)
-inline bool bias16_rows(const void* bias, int dtype, const int64_t* stride) {
-  return bias && (dtype == 16 || dtype == 17) && ((uintptr_t)bias & 15) == 0 && stride[0] % 8 == 0 &&
-         stride[1] % 8 == 0 && stride[2] % 8 == 0;
-}
 #if FA2_HP_STAMPS
 // development builds (-DFA2_HP_STAMPS=1): per-wave s_memtime sums of the hand-placed kernels,
 // accumulated into one device buffer of 16 counters (fa2_debug_hp_stamps reads and clears it)
@@ -117,18 +112,6 @@ inline unsigned long long* hp_stamp_buf() {
   return buf;
 }
 #endif
-// host side: compute units of the current device (persistent grids), cached per device id
-inline int device_cu_count() {
-  static int cached[64] = {0};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-  if (!cached[dev]) {
-    int n = 0;
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-    cached[dev] = n;
-  }
-  return cached[dev];
-}
 
 // ---------------------------------------------------------------------------------------------
 // Cross-half exchange: returns {x of lanes 0-31, x of lanes 32-63} in every lane.

@@ -1,37 +1,76 @@
-// fa2_internal.h -- launcher entry points shared between the kernel TUs and the C ABI.
+// fa2_internal.h -- what the C ABI (api.hip) and the kernel translation units share on the host:
+// the launcher entry points, the context a call hands them, and the one dispatcher that turns
+// runtime values into template arguments.  What a call launches is decided in select.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "fa2_amd.h"  // include/ (build.py passes -I)
+#include <type_traits>
+
+#include "select.h"
 
 namespace fa2 {
 
-// the fa2_policy of the fa2_fwd_ex / fa2_bwd_stages_ex call running on this thread, nullptr for
-// the defaults (api.hip; set for the duration of that call only)
-extern thread_local const fa2_policy* g_call_policy;
-inline bool path_on(uint32_t bit) { return !(g_call_policy && (g_call_policy->disable & bit)); }
-inline int capped_grid(int ncu) {
-  const int c = g_call_policy ? g_call_policy->grid_cap : 0;
-  return c > 0 && c < ncu ? c : ncu;
+// What api.hip hands every launcher besides the arguments: the stream, whether every row of every
+// 16-bit tensor is 16-byte aligned, and the fa2_policy of the call (nullptr: the defaults).  The
+// library keeps no state between calls and none per thread besides the error string.
+struct LaunchCtx {
+  hipStream_t stream;
+  bool aligned;
+  const fa2_policy* policy;
+};
+
+// dispatch(f, v1, values<a, b, ...>{}, v2, values<...>{}, ...) calls
+// f(std::integral_constant<decltype(a), a>{}, ...) with the listed constants equal to v1, v2, ...;
+// hipErrorInvalidValue when a value is not in its list.  Every combination of the lists is
+// instantiated: f rules out the ones that must not exist with `if constexpr`.
+template <auto... Vs>
+struct values {};
+using bools = values<false, true>;
+
+template <typename F>
+hipError_t dispatch(F&& f) {
+  return f();
+}
+template <typename F, typename T, auto... Vs, typename... Rest>
+hipError_t dispatch(F&& f, T v, values<Vs...>, Rest... rest) {
+  hipError_t e = hipErrorInvalidValue;
+  auto bound = [&](auto c) { return dispatch([&](auto... cs) { return f(c, cs...); }, rest...); };
+  (void)((v == Vs && ((e = bound(std::integral_constant<decltype(Vs), Vs>{})), true)) || ...);
+  return e;
+}
+using dtypes = bools;                     // BF16
+using tiles = values<32, 64, 128, 256>;  // DT (head_dim_tile)
+
+// compute units of the current device (persistent grids, the decode split heuristic), cached per
+// device id; 256 (an MI355X) when there is none to ask
+inline int device_cu_count() {
+  static int cached[64] = {0};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
+  if (!cached[dev]) {
+    int n = 0;
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+    cached[dev] = n;
+  }
+  return cached[dev];
 }
 
-// Forward, one translation unit per (dtype, head-dim tile); see fwd_inst.hip.
+// Forward and backward (fwd_kernel.h, bwd_kernel.h), one translation unit per (dtype, head-dim
+// tile): select_fwd / select_bwd, one dispatch over the plan, the launches.  stages: bit 0 delta,
+// bit 1 dK/dV, bit 2 dQ, bit 3 the bias gradient.
 template <bool BF16, int DT>
-hipError_t launch_fwd_dt(const fa2_fwd_args& a, bool aligned, hipStream_t st);
-
-// Backward: delta = rowsum(O * dO), then dK/dV (key-stationary) and dQ (query-stationary).
-// stages: bit 0 delta, bit 1 dK/dV, bit 2 dQ (7 = the whole backward).
+hipError_t launch_fwd_dt(const fa2_fwd_args& a, LaunchCtx ctx);
 template <bool BF16, int DT>
-hipError_t launch_bwd_dt(const fa2_bwd_args& a, bool aligned, int stages, hipStream_t st);
+hipError_t launch_bwd_dt(const fa2_bwd_args& a, LaunchCtx ctx, int stages);
 
 // Sliding-window (local) attention, ABI 10 (local_kernel.h): one translation unit of its own per
-// (dtype, head-dim tile).  Called by the two launchers above when a.local is set; api.hip has
-// normalised the window by then (causal folded into window_right = 0, a window that bounds
-// nothing or only restates the causal mask turned off) and rejected bias / dropout / dbias.
+// (dtype, head-dim tile).  Called by the two launchers above with a plan whose path is local;
+// api.hip has normalised the window by then (causal folded into window_right = 0, a window that
+// bounds nothing or only restates the causal mask turned off) and rejected bias / dropout / dbias.
 template <bool BF16, int DT>
-hipError_t launch_fwd_local(const fa2_fwd_args& a, bool aligned, hipStream_t st);
+hipError_t launch_fwd_local(const fa2_fwd_args& a, const FwdPlan& plan, hipStream_t st);
 template <bool BF16, int DT>
-hipError_t launch_bwd_local(const fa2_bwd_args& a, bool aligned, int stages, hipStream_t st);
+hipError_t launch_bwd_local(const fa2_bwd_args& a, const BwdPlan& plan, hipStream_t st);
 
 hipError_t launch_cu_seqlens(const uint8_t* mask, int64_t stride, int batch, int seqlen,
                              int32_t* out, hipStream_t st);
@@ -41,26 +80,14 @@ hipError_t launch_cu_seqlens(const uint8_t* mask, int64_t stride, int batch, int
 uint32_t dropout_keep_threshold(float p);
 hipError_t launch_dropout_mask(const fa2_fwd_args& a, hipStream_t st);
 
-// q-head split of dK/dV (ABI 4): the smallest divisor s of the GQA group size G = Hq / Hkv with
-// s * B * Hkv * ceil(Sk / 128) >= kDkvTargetGrid workgroups (two per CU), G if none is; 1 when
-// G == 1 or the grid is already that large.
-constexpr int kDkvTargetGrid = 512;
-inline int dkv_split_count(int B, int Hq, int Hkv, int Sk) {
-  if (B < 1 || Hkv < 1 || Hq % Hkv != 0 || Sk < 1) return 1;
-  const int G = Hq / Hkv;
-  const int64_t grid = (int64_t)((Sk + 127) / 128) * B * Hkv;
-  if (G <= 1 || grid >= kDkvTargetGrid) return 1;
-  for (int s = 2; s < G; ++s)
-    if (G % s == 0 && grid * s >= kDkvTargetGrid) return s;
-  return G;
-}
-inline int64_t dkv_workspace_bytes(int B, int Hq, int Hkv, int Sk, int D) {
-  const int s = dkv_split_count(B, Hq, Hkv, Sk);
-  return s > 1 ? 2 * (int64_t)s * B * Hkv * Sk * D * 4 : 0;
-}
-// the split a launch uses: only with a large enough workspace (checked by fa2_bwd_stages)
-inline int dkv_split(const fa2_bwd_args& a) {
-  return a.dkv_workspace ? dkv_split_count(a.batch, a.heads_q, a.heads_kv, a.seqlen_k) : 1;
-}
+// KV-cache decode over either cache layout, Args = fa2_kvcache_args or fa2_paged_kvcache_args:
+// the split attention kernel (kvcache_kernel.h, one translation unit per layout, dtype and
+// head-dim tile), the append of k_new / v_new and the combination of nsplit > 1 partial results
+// (kvcache.hip).
+template <bool BF16, int DT, typename Args>
+hipError_t launch_kvcache_split(const Args& a, int nsplit, hipStream_t st);
+template <typename Args>
+hipError_t launch_kvcache_append(const Args& a, hipStream_t st);
+hipError_t launch_kvcache_combine(const fa2_kvcache_args& a, int nsplit, hipStream_t st);
 
 }  // namespace fa2

@@ -58,56 +58,44 @@ __global__ void __launch_bounds__((FwdCfg<DT, CAUSAL>::NW * 64), (FwdCfg<DT, CAU
 }
 
 // ---------------------------------------------------------------------------------------------
-template <bool BF16, int DT, bool CAUSAL, bool BIAS, bool DROPOUT, bool ALIGNED>
+// fwd_kernel, the general forward, with every (CAUSAL, BIAS, DROP, ALIGNED)
+template <bool BF16, int DT, bool CAUSAL, bool BIAS, int DROP, bool ALIGNED>
 static hipError_t launch_fwd_t(const fa2_fwd_args& a, hipStream_t st) {
   constexpr int NW = FwdCfg<DT, CAUSAL>::NW, BM = NW * 32;
   dim3 grid(((a.seqlen_q + BM - 1) / BM) * a.batch * a.heads_q);
-  if constexpr (DROPOUT) {
-    // with a keep-mask buffer the bits are drawn by dropout_mask_kernel (all VALU, full
-    // occupancy) and read here; without one the softmax draws them
-    if (a.dropout_mask) {
-      if (hipError_t e = launch_dropout_mask(a, st); e != hipSuccess) return e;
-      hipLaunchKernelGGL((fwd_kernel<BF16, DT, CAUSAL, BIAS, 2, ALIGNED>), grid, dim3(NW * 64), 0, st, a);
-      return hipGetLastError();
-    }
-  }
-  hipLaunchKernelGGL((fwd_kernel<BF16, DT, CAUSAL, BIAS, DROPOUT ? 1 : 0, ALIGNED>), grid, dim3(NW * 64), 0, st, a);
+  hipLaunchKernelGGL((fwd_kernel<BF16, DT, CAUSAL, BIAS, DROP, ALIGNED>), grid, dim3(NW * 64), 0, st, a);
   return hipGetLastError();
 }
 
+// The plan (select_fwd), then per path one dispatch over the flags that path's kernel has: the
+// hand-placed kernel exists at DT = 128 only (no bias, aligned, dropout from keep words), the
+// pipelined one at DT 64 / 128 with BIASK 0 / 16 / 17 (aligned, no dropout).  A plan that holds
+// anything else for its path is an error.
 template <bool BF16, int DT>
-hipError_t launch_fwd_dt(const fa2_fwd_args& a, bool aligned, hipStream_t st) {
-  const bool c = a.causal != 0, bi = a.bias != nullptr, dr = a.dropout_p > 0.f;
-  // a sliding window (normalised by api.hip) comes first: no other kernel knows one
-  if (a.local) return launch_fwd_local<BF16, DT>(a, aligned, st);
-  // hot path: software-pipelined kernel (fwd_pipe_kernel.h), also with a 16-bit bias whose rows
-  // are 16-byte aligned (its tiles are staged by LDS-DMA)
-  if constexpr (DT == 128) {
-    // hand-placed one-wave-per-SIMD kernel (fwd_hp_kernel.h) for D = 128 exactly
-    if (a.head_dim == DT && fwd_hp_ok(a, aligned))
-      return c ? launch_fwd_hp<BF16, true, DT>(a, st) : launch_fwd_hp<BF16, false, DT>(a, st);
+hipError_t launch_fwd_dt(const fa2_fwd_args& a, LaunchCtx ctx) {
+  const FwdPlan p = select_fwd(a, ctx.aligned, ctx.policy);
+  if (p.path == Path::local) return launch_fwd_local<BF16, DT>(a, p, ctx.stream);
+  // with a keep-mask buffer the dropout bits are drawn by dropout_mask_kernel (all VALU, full
+  // occupancy) and read by the forward; without one the softmax draws them
+  if (p.mask_first)
+    if (hipError_t e = launch_dropout_mask(a, ctx.stream); e != hipSuccess) return e;
+  if (p.path == Path::hand_placed) {
+    if constexpr (DT == 128)
+      if (p.biask == 0 && p.drop != 1 && p.aligned)
+        return dispatch([&](auto causal, auto drop) { return launch_fwd_hp<BF16, causal.value, DT, drop.value>(a, ctx); },
+                        p.causal, bools{}, p.drop == 2, bools{});
+  } else if (p.path == Path::pipelined) {
+    if constexpr (DT == 64 || DT == 128)
+      if (p.drop == 0 && p.aligned)
+        return dispatch([&](auto causal, auto biask) { return launch_fwd_pipe<BF16, DT, causal.value, biask.value>(a, ctx.stream); },
+                        p.causal, bools{}, p.biask, values<0, 16, 17>{});
+  } else if (p.biask <= 1) {
+    return dispatch(
+        [&](auto causal, auto bias, auto drop, auto aligned) {
+          return launch_fwd_t<BF16, DT, causal.value, bias.value, drop.value, aligned.value>(a, ctx.stream);
+        },
+        p.causal, bools{}, p.biask == 1, bools{}, p.drop, values<0, 1, 2>{}, p.aligned, bools{});
   }
-  if constexpr (DT == 64 || DT == 128) {
-    const bool bias16 = bias16_rows(a.bias, a.bias_dtype, a.bias_stride);
-    if (aligned && !dr && a.k_stride[1] == a.v_stride[1] && (!bi || bias16)) {
-      if (!bi) return c ? launch_fwd_pipe<BF16, DT, true, 0>(a, st) : launch_fwd_pipe<BF16, DT, false, 0>(a, st);
-      if (a.bias_dtype == FA2_BF16)
-        return c ? launch_fwd_pipe<BF16, DT, true, 17>(a, st) : launch_fwd_pipe<BF16, DT, false, 17>(a, st);
-      return c ? launch_fwd_pipe<BF16, DT, true, 16>(a, st) : launch_fwd_pipe<BF16, DT, false, 16>(a, st);
-    }
-  }
-#define FA2_FWD_CASE(C, B, R, A)                                  \
-  if (c == C && bi == B && dr == R && aligned == A)               \
-    return launch_fwd_t<BF16, DT, C, B, R, A>(a, st);
-#define FA2_FWD_A(C, B, R) FA2_FWD_CASE(C, B, R, true) FA2_FWD_CASE(C, B, R, false)
-#define FA2_FWD_R(C, B) FA2_FWD_A(C, B, true) FA2_FWD_A(C, B, false)
-#define FA2_FWD_B(C) FA2_FWD_R(C, true) FA2_FWD_R(C, false)
-  FA2_FWD_B(true)
-  FA2_FWD_B(false)
-#undef FA2_FWD_B
-#undef FA2_FWD_R
-#undef FA2_FWD_A
-#undef FA2_FWD_CASE
   return hipErrorInvalidValue;
 }
 

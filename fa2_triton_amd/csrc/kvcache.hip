@@ -2,15 +2,17 @@
 // new key / value rows to the cache and the combination of the key splits' partial results.
 #include "common.h"
 #include "fa2_internal.h"
-#include "kvcache_host.h"
 
 namespace fa2 {
 
-// One thread per 16-byte chunk of a new row: k_new[b, n, h] -> k_cache[b, L_b + n, h] (and V), with
-// L_b = cache_seqlens[b] clamped to [0, capacity] on the device.  A row whose position is at or
-// past the capacity is dropped, so whatever cache_seqlens holds, only rows [0, capacity) of the
-// batch's own cache are written.  (dtype-blind: 16-bit elements moved as raw bits.)
-__global__ void __launch_bounds__(256) kvcache_append_kernel(const fa2_kvcache_args p) {
+// One thread per 16-byte chunk of a new row: k_new[b, n, h] -> logical row L_b + n of batch b's
+// cache (and V), with L_b = cache_seqlens[b] clamped to [0, capacity] on the device.  A row whose
+// position is at or past the capacity is dropped, so whatever cache_seqlens holds, only rows
+// [0, capacity) of a batch are written.  (dtype-blind: 16-bit elements moved as raw bits.)
+// `where(b, pos, slab, row)` is the layout: logical row pos of batch b is row `row` of slab `slab`
+// (the index of the caches' first stride).
+template <typename Where>
+FA2_DEV void kvcache_append_rows(const fa2_kvcache_args& p, Where where) {
   const int chunks = p.head_dim >> 3;
   const int64_t total = (int64_t)p.batch * p.seqlen_new * p.heads_kv * chunks;
   int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -24,45 +26,36 @@ __global__ void __launch_bounds__(256) kvcache_append_kernel(const fa2_kvcache_a
   L = min(max(L, 0), p.capacity);
   const int64_t pos = (int64_t)L + n;
   if (pos >= p.capacity) return;
+  int slab;
+  int64_t row;
+  where(b, pos, slab, row);
   const uint16_t* ks = (const uint16_t*)p.k_new + b * p.k_new_stride[0] + n * p.k_new_stride[1] + h * p.k_new_stride[2] + 8 * c;
   const uint16_t* vs = (const uint16_t*)p.v_new + b * p.v_new_stride[0] + n * p.v_new_stride[1] + h * p.v_new_stride[2] + 8 * c;
-  uint16_t* kd = (uint16_t*)p.k_cache + b * p.k_cache_stride[0] + pos * p.k_cache_stride[1] + h * p.k_cache_stride[2] + 8 * c;
-  uint16_t* vd = (uint16_t*)p.v_cache + b * p.v_cache_stride[0] + pos * p.v_cache_stride[1] + h * p.v_cache_stride[2] + 8 * c;
+  uint16_t* kd = (uint16_t*)p.k_cache + slab * p.k_cache_stride[0] + row * p.k_cache_stride[1] + h * p.k_cache_stride[2] + 8 * c;
+  uint16_t* vd = (uint16_t*)p.v_cache + slab * p.v_cache_stride[0] + row * p.v_cache_stride[1] + h * p.v_cache_stride[2] + 8 * c;
   const u32x4 kv = *(const u32x4*)ks, vv = *(const u32x4*)vs;
   *(u32x4*)kd = kv;
   *(u32x4*)vd = vv;
 }
 
-// The same append into a paged cache: logical position pos = L_b + n of batch b is row pos % P of
-// block block_table[b, pos / P], the entry clamped into [0, num_blocks - 1].  Positions at or past
-// capacity = max_blocks * P are dropped, so only table entries [0, max_blocks) are read and only
-// blocks of the pool are written, whatever cache_seqlens and the table hold.
+// contiguous cache [B, capacity, Hkv, D]: row pos of the batch's own slab
+__global__ void __launch_bounds__(256) kvcache_append_kernel(const fa2_kvcache_args p) {
+  kvcache_append_rows(p, [](int b, int64_t pos, int& slab, int64_t& row) {
+    slab = b;
+    row = pos;
+  });
+}
+
+// paged cache: row pos % P of block block_table[b, pos / P], the entry clamped into
+// [0, num_blocks - 1].  Positions at or past capacity = max_blocks * P were dropped, so only table
+// entries [0, max_blocks) are read and only blocks of the pool are written, whatever cache_seqlens
+// and the table hold.
 __global__ void __launch_bounds__(256) kvcache_paged_append_kernel(const fa2_paged_kvcache_args pp) {
-  const fa2_kvcache_args& p = pp.base;
-  const int chunks = p.head_dim >> 3;
-  const int64_t total = (int64_t)p.batch * p.seqlen_new * p.heads_kv * chunks;
-  int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= total) return;
-  const int c = (int)(idx % chunks);
-  idx /= chunks;
-  const int h = (int)(idx % p.heads_kv);
-  idx /= p.heads_kv;
-  const int n = (int)(idx % p.seqlen_new), b = (int)(idx / p.seqlen_new);
-  int L = p.cache_seqlens ? p.cache_seqlens[b] : p.capacity;
-  L = min(max(L, 0), p.capacity);
-  const int64_t pos = (int64_t)L + n;
-  if (pos >= p.capacity) return;
-  const int log_p = __builtin_ctz(pp.page_block_size);
-  int blk = pp.block_table[(int64_t)b * pp.block_table_stride + (pos >> log_p)];
-  blk = min(max(blk, 0), pp.num_blocks - 1);
-  const int64_t row = pos & (pp.page_block_size - 1);
-  const uint16_t* ks = (const uint16_t*)p.k_new + b * p.k_new_stride[0] + n * p.k_new_stride[1] + h * p.k_new_stride[2] + 8 * c;
-  const uint16_t* vs = (const uint16_t*)p.v_new + b * p.v_new_stride[0] + n * p.v_new_stride[1] + h * p.v_new_stride[2] + 8 * c;
-  uint16_t* kd = (uint16_t*)p.k_cache + blk * p.k_cache_stride[0] + row * p.k_cache_stride[1] + h * p.k_cache_stride[2] + 8 * c;
-  uint16_t* vd = (uint16_t*)p.v_cache + blk * p.v_cache_stride[0] + row * p.v_cache_stride[1] + h * p.v_cache_stride[2] + 8 * c;
-  const u32x4 kv = *(const u32x4*)ks, vv = *(const u32x4*)vs;
-  *(u32x4*)kd = kv;
-  *(u32x4*)vd = vv;
+  kvcache_append_rows(pp.base, [&](int b, int64_t pos, int& slab, int64_t& row) {
+    const int log_p = __builtin_ctz(pp.page_block_size);
+    slab = min(max(pp.block_table[(int64_t)b * pp.block_table_stride + (pos >> log_p)], 0), pp.num_blocks - 1);
+    row = pos & (pp.page_block_size - 1);
+  });
 }
 
 // Per output row (b, h, i), 64 threads (4 columns each), 4 rows per workgroup:
@@ -99,19 +92,18 @@ __global__ void __launch_bounds__(256) kvcache_combine_kernel(const fa2_kvcache_
   if ((threadIdx.x & 63) == 0 && p.lse) p.lse[row] = sum > 0.f ? m + __builtin_amdgcn_logf(sum) : kNegInf;
 }
 
-hipError_t launch_kvcache_append(const fa2_kvcache_args& a, hipStream_t st) {
+template <typename Args>
+hipError_t launch_kvcache_append(const Args& args, hipStream_t st) {
+  const fa2_kvcache_args& a = kv_base(args);
   const int64_t total = (int64_t)a.batch * a.seqlen_new * a.heads_kv * (a.head_dim >> 3);
   if (total <= 0) return hipSuccess;
-  hipLaunchKernelGGL(kvcache_append_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, a);
+  const dim3 grid((unsigned)((total + 255) / 256));
+  if constexpr (std::is_same_v<Args, fa2_paged_kvcache_args>) hipLaunchKernelGGL(kvcache_paged_append_kernel, grid, dim3(256), 0, st, args);
+  else hipLaunchKernelGGL(kvcache_append_kernel, grid, dim3(256), 0, st, args);
   return hipGetLastError();
 }
-
-hipError_t launch_kvcache_paged_append(const fa2_paged_kvcache_args& a, hipStream_t st) {
-  const int64_t total = (int64_t)a.base.batch * a.base.seqlen_new * a.base.heads_kv * (a.base.head_dim >> 3);
-  if (total <= 0) return hipSuccess;
-  hipLaunchKernelGGL(kvcache_paged_append_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, a);
-  return hipGetLastError();
-}
+template hipError_t launch_kvcache_append(const fa2_kvcache_args&, hipStream_t);
+template hipError_t launch_kvcache_append(const fa2_paged_kvcache_args&, hipStream_t);
 
 hipError_t launch_kvcache_combine(const fa2_kvcache_args& a, int nsplit, hipStream_t st) {
   const int64_t nrow = (int64_t)a.batch * a.heads_q * a.seqlen_q;

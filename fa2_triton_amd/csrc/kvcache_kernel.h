@@ -16,19 +16,21 @@
 //    [start, L_b), start = max(0, L_b - Sq - left) rounded down to a tile with a left window bound
 //    and 0 without, is cut into nsplit runs of ceil(ceil(span / 64) / nsplit) tiles.  A split whose
 //    run is empty reads no key and writes O = 0, LSE2 = -inf.  nsplit is a host function of the
-//    shapes only (kvcache_host.h), so nothing depends on the lengths on the host.
+//    shapes only (select.h), so nothing depends on the lengths on the host.
 //  * nsplit == 1: the unit writes O and LSE2.  Otherwise it writes its normalised fp32 partial O and
 //    its LSE2 into the workspace and kvcache_combine_kernel (kvcache.hip) sums them in split order.
 // Masking: every score is masked per element against the row's [lo, hi] key interval (hi <= L_b - 1),
 // which also covers the rows of a tile past L_b (staged as copies of row L_b - 1: cache rows at or
 // past L_b are never read).  A row whose running max is still -inf exponentiates against 0, so a
 // fully masked tile adds exact zeros (as the windowed forward).
-// The kernel's body is kvcache_kernel_body.h, which kvcache_paged_kernel.h includes as well (the
-// same kernel over a paged cache); the paged staging helpers are defined here.
+//
+// Paged caches (fa2_fwd_kvcache_paged): pools of blocks [num_blocks, P, Hkv, D], logical
+// key j of batch b in row j % P of block block_table[b, j / P].  kvcache_paged_split_kernel is the
+// same body (kvcache_kernel_body.h) with PAGED = true: what differs is the source address of a
+// tile's rows (stage_tile_paged) and the lookup of the block ids one step ahead (kv_page_ids).
 #pragma once
 #include "common.h"
 #include "fa2_internal.h"
-#include "kvcache_host.h"
 
 namespace fa2 {
 
@@ -47,7 +49,7 @@ FA2_DEV void vm_wait_but() {
 FA2_DEV void lds_wait_all() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 
 // What the shared body (kvcache_kernel_body.h) names `pg`: the paging fields of
-// fa2_paged_kvcache_args in the paged kernel (kvcache_paged_kernel.h), this empty stand-in here
+// fa2_paged_kvcache_args in the paged kernel, this empty stand-in in the contiguous one
 // (read only inside `if constexpr (PAGED)`, which the contiguous kernel discards).
 struct KvNoPages {
   const int32_t* block_table = nullptr;
@@ -126,9 +128,20 @@ __global__ void __launch_bounds__(KvCfg<DT>::NW * 64) kvcache_split_kernel(const
 }
 
 template <bool BF16, int DT>
-hipError_t launch_kvcache_split(const fa2_kvcache_args& a, int nsplit, hipStream_t st) {
-  const int64_t grid = kv_units(a) * nsplit;
-  hipLaunchKernelGGL((kvcache_split_kernel<BF16, DT>), dim3((unsigned)grid), dim3(KvCfg<DT>::NW * 64), 0, st, a, nsplit);
+__global__ void __launch_bounds__(KvCfg<DT>::NW * 64) kvcache_paged_split_kernel(const fa2_paged_kvcache_args pg, const int nsplit) {
+  constexpr bool PAGED = true;
+  const fa2_kvcache_args& p = pg.base;
+#include "kvcache_kernel_body.h"
+}
+
+// One launcher for both layouts: the kernel follows from the argument struct.
+template <bool BF16, int DT, typename Args>
+hipError_t launch_kvcache_split(const Args& a, int nsplit, hipStream_t st) {
+  const dim3 grid((unsigned)(kv_units(kv_base(a)) * nsplit)), block(KvCfg<DT>::NW * 64);
+  if constexpr (std::is_same_v<Args, fa2_paged_kvcache_args>)
+    hipLaunchKernelGGL((kvcache_paged_split_kernel<BF16, DT>), grid, block, 0, st, a, nsplit);
+  else
+    hipLaunchKernelGGL((kvcache_split_kernel<BF16, DT>), grid, block, 0, st, a, nsplit);
   return hipGetLastError();
 }
 

@@ -1,7 +1,7 @@
 // kvcache_kernel_body.h -- the body of the KV-cache decode kernel, shared textually by the two
-// __global__ functions that run it: kvcache_split_kernel (kvcache_kernel.h, PAGED = false, the
-// contiguous [B, capacity, Hkv, D] cache) and kvcache_paged_split_kernel (kvcache_paged_kernel.h,
-// PAGED = true, a pool of blocks addressed through a block table).  In scope at the point of
+// __global__ functions of kvcache_kernel.h that run it: kvcache_split_kernel (PAGED = false, the
+// contiguous [B, capacity, Hkv, D] cache) and kvcache_paged_split_kernel (PAGED = true, a pool of
+// blocks addressed through a block table).  In scope at the point of
 // inclusion: the constants BF16, DT, PAGED, the arguments `p` (fa2_kvcache_args) and `nsplit`, and
 // `pg` with the paging fields (block_table, block_table_stride, page_block_size, num_blocks).
 // Included text rather than a __device__ function template: DESIGN 11 records what that route did

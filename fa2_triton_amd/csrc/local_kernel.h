@@ -56,40 +56,38 @@ __global__ void __launch_bounds__(256, DT >= 256 ? 1 : 2) dkdv_local_kernel(cons
 }
 
 template <bool BF16, int DT>
-hipError_t launch_fwd_local(const fa2_fwd_args& a, bool aligned, hipStream_t st) {
+hipError_t launch_fwd_local(const fa2_fwd_args& a, const FwdPlan& plan, hipStream_t st) {
   constexpr int NW = FwdCfg<DT, true>::NW, BM = NW * 32;
   dim3 grid(((a.seqlen_q + BM - 1) / BM) * a.batch * a.heads_q);
-  if (aligned) hipLaunchKernelGGL((fwd_local_kernel<BF16, DT, true>), grid, dim3(NW * 64), 0, st, a);
-  else hipLaunchKernelGGL((fwd_local_kernel<BF16, DT, false>), grid, dim3(NW * 64), 0, st, a);
-  return hipGetLastError();
+  return dispatch(
+      [&](auto aligned) {
+        hipLaunchKernelGGL((fwd_local_kernel<BF16, DT, aligned.value>), grid, dim3(NW * 64), 0, st, a);
+        return hipGetLastError();
+      },
+      plan.aligned, bools{});
 }
 
-// stages as launch_bwd_t: bit 0 the standalone delta, bit 2 dQ (writes delta too), bit 1 dK/dV
-// (the bias gradient, bit 3, is rejected with a window)
+// the stages of select_bwd's plan for a window: the standalone delta, dQ (writes delta too), dK/dV
+// (the bias gradient is rejected with a window)
 template <bool BF16, int DT>
-hipError_t launch_bwd_local(const fa2_bwd_args& a, bool aligned, int stages, hipStream_t st) {
-  if ((stages & 1) && a.lse_row_stride > 0) {
-    dim3 grid((a.lse_row_stride + 15) / 16, a.batch * a.heads_q);
-    if (aligned) hipLaunchKernelGGL((delta_kernel<BF16, true>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((delta_kernel<BF16, false>), grid, dim3(256), 0, st, a);
-  }
-  if ((stages & 4) && a.seqlen_q > 0) {
-    constexpr int NW = DqCfg<DT>::NW, BM = NW * 32;
-    dim3 grid(((a.seqlen_q + BM - 1) / BM) * a.batch * a.heads_q);
-    auto dq = [&](auto aligned_c, auto f32_c) {
-      hipLaunchKernelGGL((dq_local_kernel<BF16, DT, decltype(aligned_c)::value, decltype(f32_c)::value>), grid,
-                         dim3(NW * 64), 0, st, a);
-    };
-    const bool f32 = a.dq_dtype == FA2_F32;
-    if (aligned) f32 ? dq(std::true_type{}, std::true_type{}) : dq(std::true_type{}, std::false_type{});
-    else f32 ? dq(std::false_type{}, std::true_type{}) : dq(std::false_type{}, std::false_type{});
-  }
-  if ((stages & 2) && a.seqlen_k > 0) {
-    dim3 grid(((a.seqlen_k + 127) / 128) * a.batch * a.heads_kv);
-    if (aligned) hipLaunchKernelGGL((dkdv_local_kernel<BF16, DT, true>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((dkdv_local_kernel<BF16, DT, false>), grid, dim3(256), 0, st, a);
-  }
-  return hipGetLastError();
+hipError_t launch_bwd_local(const fa2_bwd_args& a, const BwdPlan& plan, hipStream_t st) {
+  return dispatch(
+      [&](auto aligned, auto f32) {
+        for (int i = 0; i < plan.nstages; ++i) {
+          if (plan.stage[i].kind == Stage::delta) {
+            launch_delta<BF16, aligned.value>(a, st);
+          } else if (plan.stage[i].kind == Stage::dq) {
+            constexpr int NW = DqCfg<DT>::NW, BM = NW * 32;
+            dim3 grid(((a.seqlen_q + BM - 1) / BM) * a.batch * a.heads_q);
+            hipLaunchKernelGGL((dq_local_kernel<BF16, DT, aligned.value, f32.value>), grid, dim3(NW * 64), 0, st, a);
+          } else if (plan.stage[i].kind == Stage::dkdv) {
+            dim3 grid(((a.seqlen_k + 127) / 128) * a.batch * a.heads_kv);
+            hipLaunchKernelGGL((dkdv_local_kernel<BF16, DT, aligned.value>), grid, dim3(256), 0, st, a);
+          }
+        }
+        return hipGetLastError();
+      },
+      plan.aligned, bools{}, plan.dq_f32, bools{});
 }
 
 }  // namespace fa2

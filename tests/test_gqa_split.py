@@ -20,7 +20,7 @@ import torch
 from fa2_triton_amd import _lib
 from tests.core import generate_test_data, run_case
 
-TARGET = 512  # kDkvTargetGrid (fa2_internal.h): two dK/dV workgroups per CU
+TARGET = 512  # kDkvTargetGrid (select.h): two dK/dV workgroups per CU
 
 
 def _expected_split(b, hq, hkv, sk):
