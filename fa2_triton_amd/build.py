@@ -33,8 +33,10 @@ def hipcc() -> str:
 
 
 # The generated units, one per (unit prefix, dtype, tile): (prefix, header, explicit instantiations
-# of the launchers that header defines); {bf} and {dt} are the unit's template arguments.  Each
-# family has units of its own so that none of the others grows.
+# of the launchers that header defines[, the tiles the family exists for: all of TILES when left
+# out]); {bf} and {dt} are the unit's template arguments.  Each family has units of its own so that
+# none of the others grows.
+FP8_TILES = (64, 128)
 UNITS = (
     ("fwd", "fwd_kernel.h", ("launch_fwd_dt<{bf}, {dt}>(const fa2_fwd_args&, LaunchCtx)",)),
     ("bwd", "bwd_kernel.h", ("launch_bwd_dt<{bf}, {dt}>(const fa2_bwd_args&, LaunchCtx, int)",)),
@@ -43,15 +45,19 @@ UNITS = (
     ("kvcache", "kvcache_kernel.h", ("launch_kvcache_split<{bf}, {dt}>(const fa2_kvcache_args&, int, hipStream_t)",)),
     ("kvcache_paged", "kvcache_kernel.h",
      ("launch_kvcache_split<{bf}, {dt}>(const fa2_paged_kvcache_args&, int, hipStream_t)",)),
+    ("kvcache_fp8", "kvcache_fp8_kernel.h",
+     ("launch_kvcache_fp8_split<{bf}, {dt}, false>(const fa2_fp8_kvcache_args&, int, hipStream_t)",), FP8_TILES),
+    ("kvcache_fp8_paged", "kvcache_fp8_kernel.h",
+     ("launch_kvcache_fp8_split<{bf}, {dt}, true>(const fa2_fp8_kvcache_args&, int, hipStream_t)",), FP8_TILES),
 )
 
 
 def generated_sources():
     os.makedirs(GEN, exist_ok=True)
     srcs = []
-    for prefix, header, insts in UNITS:
+    for prefix, header, insts, *only in UNITS:
         for dname, flag in DTYPES.items():
-            for dt in TILES:
+            for dt in (only[0] if only else TILES):
                 path = os.path.join(GEN, f"{prefix}_{dname}_d{dt}.hip")
                 lines = "".join(f"template hipError_t {i.format(bf=flag, dt=dt)};\n" for i in insts)
                 body = f'#include "../{header}"\nnamespace fa2 {{\n{lines}}}\n'
@@ -127,7 +133,7 @@ def build(force: bool = False, jobs: int = 0) -> str:
     os.makedirs(OBJ, exist_ok=True)
     generated_headers()
     srcs = [os.path.join(CSRC, "api.hip"), os.path.join(CSRC, "misc.hip"),
-            os.path.join(CSRC, "kvcache.hip")] + generated_sources()
+            os.path.join(CSRC, "kvcache.hip"), os.path.join(CSRC, "kvcache_fp8.hip")] + generated_sources()
     dep_t = deps_mtime()
     jobs = jobs or min(16, os.cpu_count() or 4)
     with ThreadPoolExecutor(max_workers=jobs) as ex:

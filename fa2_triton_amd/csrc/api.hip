@@ -112,15 +112,18 @@ int check_policy(const fa2_policy* p) {
 // Everything fa2_fwd_kvcache checks after the sizes, shared with the paged call (whose pools are
 // k_cache / v_cache with block, row and head strides): pointers, the new rows, 16-byte rows, the
 // workspace and the grid.  On success *nsplit_out is the split count of the call.
-int kvcache_check_call(const fa2_kvcache_args* a, int* nsplit_out) {
+// fp8: the caches hold bytes (fa2_fwd_kvcache_fp8): head_dim a multiple of 16 and cache strides of 16.
+int kvcache_check_call(const fa2_kvcache_args* a, int* nsplit_out, bool fp8 = false) {
   if (!a->q || !a->k_cache || !a->v_cache || !a->o) return fail(FA2_E_INVALID, "null tensor pointer");
   if ((a->k_new != nullptr) != (a->v_new != nullptr)) return fail(FA2_E_INVALID, "k_new and v_new must be given together");
   if (a->k_new ? a->seqlen_new < 1 : a->seqlen_new != 0)
     return fail(FA2_E_INVALID, "seqlen_new=%d %s k_new / v_new", a->seqlen_new, a->k_new ? "with" : "without");
   const int D = a->head_dim;
-  if (D % 8 != 0) return fail(FA2_E_UNSUPPORTED, "head_dim %d is not a multiple of 8 (16-byte rows)", D);
-  bool aligned = vec_ok(D, a->q, a->q_stride) && vec_ok(D, a->k_cache, a->k_cache_stride) &&
-                 vec_ok(D, a->v_cache, a->v_cache_stride) && vec_ok(D, a->o, a->o_stride);
+  if (D % (fp8 ? 16 : 8) != 0)
+    return fail(FA2_E_UNSUPPORTED, "head_dim %d is not a multiple of %d (16-byte rows)", D, fp8 ? 16 : 8);
+  bool aligned = vec_ok(D, a->q, a->q_stride) && vec_ok(D, a->o, a->o_stride);
+  if (fp8) aligned = aligned && fa2::fp8_rows16(a->k_cache, a->k_cache_stride) && fa2::fp8_rows16(a->v_cache, a->v_cache_stride);
+  else aligned = aligned && vec_ok(D, a->k_cache, a->k_cache_stride) && vec_ok(D, a->v_cache, a->v_cache_stride);
   if (a->k_new) aligned = aligned && vec_ok(D, a->k_new, a->k_new_stride) && vec_ok(D, a->v_new, a->v_new_stride);
   if (!aligned) return fail(FA2_E_UNSUPPORTED, "a tensor's rows are not 16-byte aligned (pointer or strides)");
   const int nsplit = fa2_kvcache_num_splits(a);
@@ -162,6 +165,33 @@ int paged_kvcache_check_sizes(const fa2_paged_kvcache_args* a) {
   if (a->num_blocks < 1) return fail(FA2_E_INVALID, "num_blocks=%d must be >= 1", a->num_blocks);
   if (a->base.capacity % P != 0)
     return fail(FA2_E_INVALID, "capacity=%d must be max_blocks * page_block_size (a multiple of %d)", a->base.capacity, P);
+  return FA2_OK;
+}
+
+// fp8 caches: the sizes of the base call (with a block table, of the paged call), then the head
+// dim the fp8 kernels cover.
+int fp8_kvcache_check_sizes(const fa2_fp8_kvcache_args* a) {
+  if (int rc = fa2::fp8_paged(*a) ? paged_kvcache_check_sizes(&a->paged) : kvcache_check_sizes(&a->paged.base)) return rc;
+  if (!fa2::fp8_head_dim_tile(a->paged.base.head_dim))
+    return fail(FA2_E_UNSUPPORTED, "head_dim %d > %d with fp8 caches", a->paged.base.head_dim, fa2::kFp8MaxHeadDim);
+  return FA2_OK;
+}
+
+// The fp8 call (its sizes checked): run_kvcache's steps with the fp8 kernels; the combination is
+// the 16-bit call's.
+int run_fp8_kvcache(const fa2_fp8_kvcache_args& args, void* stream) {
+  const fa2_kvcache_args& a = args.paged.base;
+  int nsplit = 1;
+  if (int rc = kvcache_check_call(&a, &nsplit, true)) return rc;
+  const char* entry = "fa2_fwd_kvcache_fp8";
+  hipStream_t st = (hipStream_t)stream;
+  if (a.k_new)
+    if (int rc = hip_status(fa2::launch_kvcache_fp8_append(args, st), entry, "append launch")) return rc;
+  const hipError_t e = fa2::dispatch(
+      [&](auto bf, auto dt, auto paged) { return fa2::launch_kvcache_fp8_split<bf.value, dt.value, paged.value>(args, nsplit, st); },
+      a.dtype == FA2_BF16, fa2::dtypes{}, fa2::fp8_head_dim_tile(a.head_dim), fa2::fp8_tiles{}, fa2::fp8_paged(args), fa2::bools{});
+  if (int rc = hip_status(e, entry, "launch")) return rc;
+  if (nsplit > 1) return hip_status(fa2::launch_kvcache_combine(a, nsplit, st), entry, "combine launch");
   return FA2_OK;
 }
 }  // namespace
@@ -310,6 +340,33 @@ int fa2_fwd_kvcache_paged(const fa2_paged_kvcache_args* a, void* stream) {
     return fail(FA2_E_INVALID, "block_table_stride %lld < max_blocks %lld (capacity / page_block_size)",
                 (long long)a->block_table_stride, (long long)max_blocks);
   return run_kvcache(*a, "fa2_fwd_kvcache_paged", stream);
+}
+
+int fa2_fp8_kvcache_num_splits(const fa2_fp8_kvcache_args* a) {
+  if (!a || fp8_kvcache_check_sizes(a)) return 1;
+  return fa2_kvcache_num_splits(&a->paged.base);
+}
+
+int64_t fa2_fp8_kvcache_workspace_bytes(const fa2_fp8_kvcache_args* a) {
+  if (!a || fp8_kvcache_check_sizes(a)) return 0;
+  return fa2_kvcache_workspace_bytes(&a->paged.base);
+}
+
+int fa2_fwd_kvcache_fp8(const fa2_fp8_kvcache_args* args, void* stream) {
+  touch_thread_state();
+  if (!args) return fail(FA2_E_INVALID, "null args");
+  if (int rc = fp8_kvcache_check_sizes(args)) return rc;
+  const fa2_kvcache_args& a = args->paged.base;
+  if (fa2::fp8_paged(*args)) {
+    const int64_t max_blocks = a.capacity / args->paged.page_block_size;
+    if (args->paged.block_table_stride < max_blocks)
+      return fail(FA2_E_INVALID, "block_table_stride %lld < max_blocks %lld (capacity / page_block_size)",
+                  (long long)args->paged.block_table_stride, (long long)max_blocks);
+  }
+  if (((uintptr_t)args->k_descale | (uintptr_t)args->v_descale) & 3) return fail(FA2_E_INVALID, "k_descale / v_descale must be 4-byte aligned");
+  for (const int64_t* s : {args->k_descale_stride, args->v_descale_stride})
+    if (s[0] < 0 || s[1] < 0) return fail(FA2_E_INVALID, "negative descale stride (%lld, %lld)", (long long)s[0], (long long)s[1]);
+  return run_fp8_kvcache(*args, stream);
 }
 
 #if FA2_HP_STAMPS

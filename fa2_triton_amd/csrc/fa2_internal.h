@@ -90,4 +90,12 @@ template <typename Args>
 hipError_t launch_kvcache_append(const Args& a, hipStream_t st);
 hipError_t launch_kvcache_combine(const fa2_kvcache_args& a, int nsplit, hipStream_t st);
 
+// The same over fp8 caches (fa2_fp8_kvcache_args): the split kernel
+// (kvcache_fp8_kernel.h, one translation unit per layout, dtype and head-dim tile of fp8_tiles) and
+// the quantising append (kvcache_fp8.hip).  The combination is launch_kvcache_combine.
+using fp8_tiles = values<64, 128>;  // DT (fp8_head_dim_tile)
+template <bool BF16, int DT, bool PAGED>
+hipError_t launch_kvcache_fp8_split(const fa2_fp8_kvcache_args& a, int nsplit, hipStream_t st);
+hipError_t launch_kvcache_fp8_append(const fa2_fp8_kvcache_args& a, hipStream_t st);
+
 }  // namespace fa2

@@ -231,4 +231,18 @@ inline int64_t kv_workspace_bytes(const fa2_kvcache_args& a, int nsplit) {
   return (int64_t)nsplit * a.batch * a.heads_q * a.seqlen_q * ((int64_t)a.head_dim + 1) * 4;
 }
 
+// ---------------------------------------------------------------------------------------------
+// fp8 caches (kvcache_fp8_kernel.h): the kernels exist for the head-dim tiles 64 and 128 (a tile's
+// rows are DT bytes, 16-byte pieces of 16 elements) and both layouts.  Units, splits and workspace
+// are those of `paged.base` above.
+constexpr int kFp8MaxHeadDim = 128;
+// head-dim tile of the fp8 kernels' DT; 0: head_dim > 128
+inline int fp8_head_dim_tile(int d) { return d <= 64 ? 64 : d <= kFp8MaxHeadDim ? 128 : 0; }
+// a NULL block table is the contiguous layout
+inline bool fp8_paged(const fa2_fp8_kvcache_args& a) { return a.paged.block_table != nullptr; }
+// every row of a byte cache starts on a 16-byte boundary
+inline bool fp8_rows16(const void* cache, const int64_t* stride) {
+  return ((uintptr_t)cache & 15) == 0 && stride[0] % 16 == 0 && stride[1] % 16 == 0 && stride[2] % 16 == 0;
+}
+
 }  // namespace fa2

@@ -1,6 +1,8 @@
 """KV-cache decode attention: `flash_attn_with_kvcache` (C ABI `fa2_fwd_kvcache`, ABI 10 minor 1)
 over one contiguous cache slab per sequence, and `flash_attn_with_paged_kvcache`
-(`fa2_fwd_kvcache_paged`) over a pool of fixed-size blocks addressed through a block table.
+(`fa2_fwd_kvcache_paged`) over a pool of fixed-size blocks addressed through a block table, and
+`flash_attn_with_fp8_kvcache` (`fa2_fwd_kvcache_fp8`) over caches of either layout that hold
+`float8_e4m3fn` bytes with a descale per (batch, kv head).
 
 One query token, or a few, per sequence against a pre-allocated key / value cache whose sequences
 have their own filled lengths.  The lengths stay on the device: nothing here reads a tensor's
@@ -32,9 +34,10 @@ def _check_plain_args(k, v, window_size, num_splits, cache_seqlens) -> Tuple[int
     return min(max(left, -1), 2**30), min(max(right, -1), 2**30)
 
 
-def _check_tensors(q, k_cache, v_cache, k, v, cache_shape: str):
+def _check_tensors(q, k_cache, v_cache, k, v, cache_shape: str, cache_dtype=None, max_head_dim: int = 256):
     """The checks both cache layouts share: q, the two caches and the optional new rows.  Returns
-    (batch, seqlen_q, heads_q, head_dim, heads_kv, new) with `new` the (name, tensor) pairs of k, v."""
+    (batch, seqlen_q, heads_q, head_dim, heads_kv, new) with `new` the (name, tensor) pairs of k, v.
+    cache_dtype: the dtype the caches must have when it is not q's (the fp8 call)."""
     for name, t in (("q", q), ("k_cache", k_cache), ("v_cache", v_cache)):
         if not isinstance(t, Tensor) or t.dim() != 4:
             raise ValueError(f"{name} must be a 4-d tensor [{'batch, seqlen' if name == 'q' else cache_shape}, heads, head_dim]")
@@ -57,15 +60,18 @@ def _check_tensors(q, k_cache, v_cache, k, v, cache_shape: str):
     if q.dtype not in (torch.float16, torch.bfloat16):
         raise TypeError(f"only fp16 and bf16 are supported, got {q.dtype}")
     for name, t in tensors:
-        if t.dtype != q.dtype:
+        if cache_dtype is not None and name.endswith("_cache"):
+            if t.dtype != cache_dtype:
+                raise TypeError(f"{name} is {t.dtype}: the caches must be {cache_dtype}")
+        elif t.dtype != q.dtype:
             raise TypeError(f"{name} is {t.dtype}, q is {q.dtype}: all tensors must have the same dtype")
     for name, t in tensors:
         if not t.is_cuda or t.device != q.device:
             raise ValueError(f"{name} must be on q's GPU device, got {t.device}")
         if t.stride(-1) != 1:
             raise ValueError(f"{name} must have a unit head-dim stride")
-    if head_dim > 256:
-        raise NotImplementedError(f"{head_dim = } > 256 is not supported")
+    if head_dim > max_head_dim:
+        raise NotImplementedError(f"{head_dim = } > {max_head_dim} is not supported")
     return batch, seqlen_q, heads_q, head_dim, heads_kv, new
 
 
@@ -78,6 +84,33 @@ def _seqlens_on_device(cache_seqlens, batch: int, cap: int, device) -> Optional[
     if cache_seqlens is None:
         return None
     return torch.full((batch,), min(max(cache_seqlens, 0), cap), dtype=torch.int32, device=device)
+
+
+def _check_block_table(block_table, k_cache, q) -> int:
+    """The block table of a paged call against its pool and q; returns the capacity max_blocks * P."""
+    batch, page = q.shape[0], k_cache.shape[1]
+    if page < 16 or page & (page - 1):
+        raise ValueError(f"page_block_size (k_cache.shape[1] = {page}) must be a power of two >= 16")
+    if block_table.dtype != torch.int32:
+        raise TypeError(f"block_table must be int32, got {block_table.dtype}")
+    if block_table.shape[0] != batch or block_table.shape[1] < 1:
+        raise ValueError(f"block_table must be [batch={batch}, max_blocks >= 1], got {tuple(block_table.shape)}")
+    if block_table.device != q.device:
+        raise ValueError(f"block_table must be on q's GPU device, got {block_table.device}")
+    if block_table.stride(1) != 1 and block_table.shape[1] > 1:
+        raise ValueError("block_table must have a unit stride in its last dimension")
+    cap = block_table.shape[1] * page
+    if cap > 2**30:
+        raise NotImplementedError(f"max_blocks * page_block_size = {cap} > 2^30 is not supported")
+    return cap
+
+
+def _fill_paging(paged, block_table, k_cache) -> None:
+    """The paging fields of a fa2_paged_kvcache_args."""
+    batch, max_blocks = block_table.shape
+    paged.block_table = block_table.data_ptr()
+    paged.block_table_stride = block_table.stride(0) if batch > 1 else max(block_table.stride(0), max_blocks)
+    paged.page_block_size, paged.num_blocks = k_cache.shape[1], k_cache.shape[0]
 
 
 def _run(args, base, workspace_bytes, entry, q, k_cache, v_cache, new, seqlens, cap, softmax_scale, causal, left, right,
@@ -135,7 +168,8 @@ def flash_attn_with_kvcache(
 
     Inference only: no autograd graph is built and the result never requires grad, whatever the
     inputs require.  For paged caches (a pool of blocks and a block table) see
-    `flash_attn_with_paged_kvcache`.  Not implemented: rotary embedding, bias, dropout, backward.
+    `flash_attn_with_paged_kvcache`, for fp8 caches `flash_attn_with_fp8_kvcache`.  Not implemented:
+    rotary embedding, bias, dropout, backward.
 
     cache_seqlens: None (every sequence is `cap` long), a Python int, or an int32 device tensor [B]
         that is read on the device; each value is clamped to [0, cap].  It is not modified.
@@ -180,8 +214,9 @@ def flash_attn_with_paged_kvcache(
     [N, Hkv, P, D] and viewed [N, P, Hkv, D] needs no copy) and logical key j of batch b is row
     j % P of block `block_table[b, j // P]`.  P is a power of two >= 16.
 
-    Inference only, as the contiguous function.  Not implemented: rotary embedding, a batch-index
-    indirection, fp8 caches, page sizes that are not powers of two, bias, dropout, backward.
+    Inference only, as the contiguous function.  fp8 pools: `flash_attn_with_fp8_kvcache`.  Not
+    implemented: rotary embedding, a batch-index indirection, page sizes that are not powers of two,
+    bias, dropout, backward.
 
     block_table: int32 device tensor [B, max_blocks] with a unit stride in its last dimension (a
         column slice of a wider table is fine).  The capacity of a sequence is max_blocks * P.
@@ -207,26 +242,108 @@ def flash_attn_with_paged_kvcache(
     if not isinstance(block_table, Tensor) or block_table.dim() != 2:
         raise ValueError("block_table must be a 2-d int32 tensor [batch, max_blocks]")
     batch, _, _, _, _, new = _check_tensors(q, k_cache, v_cache, k, v, "num_blocks, page_block_size")
-    num_blocks, page = k_cache.shape[0], k_cache.shape[1]
-    if page < 16 or page & (page - 1):
-        raise ValueError(f"page_block_size (k_cache.shape[1] = {page}) must be a power of two >= 16")
-    if block_table.dtype != torch.int32:
-        raise TypeError(f"block_table must be int32, got {block_table.dtype}")
-    if block_table.shape[0] != batch or block_table.shape[1] < 1:
-        raise ValueError(f"block_table must be [batch={batch}, max_blocks >= 1], got {tuple(block_table.shape)}")
-    if block_table.device != q.device:
-        raise ValueError(f"block_table must be on q's GPU device, got {block_table.device}")
-    if block_table.stride(1) != 1 and block_table.shape[1] > 1:
-        raise ValueError("block_table must have a unit stride in its last dimension")
-    max_blocks = block_table.shape[1]
-    cap = max_blocks * page
-    if cap > 2**30:
-        raise NotImplementedError(f"max_blocks * page_block_size = {cap} > 2^30 is not supported")
+    cap = _check_block_table(block_table, k_cache, q)
     seqlens = _seqlens_on_device(cache_seqlens, batch, cap, q.device)
     lib = _lib.load()
     args = _lib.PagedKvCacheArgs()
-    args.block_table = block_table.data_ptr()
-    args.block_table_stride = block_table.stride(0) if batch > 1 else max(block_table.stride(0), max_blocks)
-    args.page_block_size, args.num_blocks = page, num_blocks
+    _fill_paging(args, block_table, k_cache)
     return _run(args, args.base, lib.fa2_paged_kvcache_workspace_bytes, lib.fa2_fwd_kvcache_paged, q, k_cache, v_cache,
+                new, seqlens, cap, softmax_scale, causal, left, right, num_splits, return_lse)
+
+
+def _check_descale(name: str, d) -> None:
+    """A descale judged without looking at a tensor: None, a float > 0 or a tensor."""
+    if d is None or isinstance(d, Tensor):
+        return
+    if isinstance(d, bool) or not isinstance(d, (int, float)):
+        raise TypeError(f"{name} must be None, a float > 0 or an fp32 tensor, got {type(d).__name__}")
+    if not (d > 0 and math.isfinite(d)):
+        raise ValueError(f"{name} must be a finite float > 0, got {d!r}")
+
+
+def _descale_on_device(name: str, d, batch: int, heads_kv: int, device) -> Optional[Tensor]:
+    """None (1.0), or an fp32 [batch, heads_kv] view on `device` (strides may be 0)."""
+    if d is None:
+        return None
+    if not isinstance(d, Tensor):
+        return torch.full((1, 1), float(d), dtype=torch.float32, device=device).expand(batch, heads_kv)
+    if d.dtype != torch.float32:
+        raise TypeError(f"{name} must be an fp32 tensor, got {d.dtype}")
+    if d.device != device:
+        raise ValueError(f"{name} must be on q's GPU device, got {d.device}")
+    try:
+        d = d.expand(batch, heads_kv) if d.dim() <= 2 else None
+    except RuntimeError:
+        d = None
+    if d is None:
+        raise ValueError(f"{name} must be broadcastable to [batch={batch}, heads_kv={heads_kv}]")
+    return d
+
+
+def flash_attn_with_fp8_kvcache(
+    q: Tensor,
+    k_cache: Tensor,
+    v_cache: Tensor,
+    k_descale: Union[None, float, Tensor] = None,
+    v_descale: Union[None, float, Tensor] = None,
+    block_table: Optional[Tensor] = None,
+    cache_seqlens: Union[None, int, Tensor] = None,
+    k: Optional[Tensor] = None,
+    v: Optional[Tensor] = None,
+    softmax_scale: Optional[float] = None,
+    causal: bool = False,
+    window_size: Tuple[int, int] = (-1, -1),
+    num_splits: int = 0,
+    return_lse: bool = False,
+):
+    """`flash_attn_with_kvcache` (with `block_table`: `flash_attn_with_paged_kvcache`) over caches that
+    hold `torch.float8_e4m3fn` bytes: half the bytes of a 16-bit cache, on the path that is bound by
+    reading them.  q, the new rows and the result are fp16 or bf16; head_dim is a multiple of 16 up
+    to 128 and every cache row must start on a 16-byte boundary.
+
+    Inference only: no autograd graph is built and the result never requires grad.  Not implemented:
+    e5m2 or fnuz caches, fp8 q, per-token or per-block scales, head dims above 128, rotary embedding,
+    a batch-index indirection.
+
+    k_descale, v_descale: the value of a cache element is its exact e4m3 value times the descale of
+        its (batch, kv head): None (1.0), a Python float > 0, or an fp32 device tensor broadcastable
+        to [B, Hkv] (an expanded view is fine) that is read on the device.  The scores are
+        (softmax_scale * k_descale) * q . k8 and the result is v_descale * (P v8), scaled in fp32
+        before its one rounding; K and V themselves are converted exactly, never scaled.
+    block_table: None for contiguous caches [B, cap, Hkv, D]; with an int32 table [B, max_blocks]
+        the caches are pools [num_blocks, P, Hkv, D], `cache_seqlens` is required and the rules are
+        those of `flash_attn_with_paged_kvcache`.
+    k, v: optional new rows [B, Sn, Hkv, D] in q's dtype, quantised on the way into the caches:
+        the byte written is e4m3(clamp(float(x) / descale, -448, 448)), rounded to nearest even, NaN
+        kept.  Attention in the same call reads the quantised bytes.
+    cache_seqlens, softmax_scale, causal, window_size, num_splits, return_lse: as
+        `flash_attn_with_kvcache`.
+
+    Returns `out` [B, Sq, Hq, D] in q's dtype, or `(out, lse)`.  With descales that are powers of two
+    the same bits as the 16-bit call on `k_cache.to(q.dtype)`, `v_cache.to(q.dtype)` with
+    softmax_scale * k_descale, times v_descale.
+    """
+    _check_descale("k_descale", k_descale)
+    _check_descale("v_descale", v_descale)
+    if block_table is not None and cache_seqlens is None:
+        raise TypeError("cache_seqlens is required with a paged cache: an int or an int32 tensor")
+    left, right = _check_plain_args(k, v, window_size, num_splits, cache_seqlens)
+    paged = block_table is not None
+    if paged and (not isinstance(block_table, Tensor) or block_table.dim() != 2):
+        raise ValueError("block_table must be a 2-d int32 tensor [batch, max_blocks]")
+    batch, _, _, _, heads_kv, new = _check_tensors(q, k_cache, v_cache, k, v, "num_blocks, page_block_size" if paged else "batch, cap",
+                                                   cache_dtype=torch.float8_e4m3fn, max_head_dim=128)
+    cap = _check_block_table(block_table, k_cache, q) if paged else k_cache.shape[1]
+    kd = _descale_on_device("k_descale", k_descale, batch, heads_kv, q.device)
+    vd = _descale_on_device("v_descale", v_descale, batch, heads_kv, q.device)
+    seqlens = _seqlens_on_device(cache_seqlens, batch, cap, q.device)
+    lib = _lib.load()
+    args = _lib.Fp8KvCacheArgs()
+    if paged:
+        _fill_paging(args.paged, block_table, k_cache)
+    for name, d in (("k_descale", kd), ("v_descale", vd)):
+        if d is not None:
+            setattr(args, name, d.data_ptr())
+            getattr(args, name + "_stride")[:] = (d.stride(0) if batch > 1 else 0, d.stride(1) if heads_kv > 1 else 0)
+    return _run(args, args.paged.base, lib.fa2_fp8_kvcache_workspace_bytes, lib.fa2_fwd_kvcache_fp8, q, k_cache, v_cache,
                 new, seqlens, cap, softmax_scale, causal, left, right, num_splits, return_lse)

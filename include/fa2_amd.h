@@ -289,6 +289,35 @@ int fa2_fwd_kvcache_paged(const fa2_paged_kvcache_args* args, void* stream);
 int fa2_paged_kvcache_num_splits(const fa2_paged_kvcache_args* args);
 int64_t fa2_paged_kvcache_workspace_bytes(const fa2_paged_kvcache_args* args);
 
+/* The same attention over fp8 caches (added within ABI 10 minor 1: detect it by the presence of the
+ * symbol fa2_fwd_kvcache_fp8).  k_cache / v_cache of `paged.base` hold OCP e4m3fn bytes; q, o and
+ * the new rows keep `paged.base.dtype` (fp16 or bf16).  A NULL paged.block_table means the
+ * contiguous layout [B, capacity, Hkv, D] (the paging fields are then ignored), otherwise the
+ * caches are pools as in fa2_fwd_kvcache_paged.  Cache strides are in elements, here bytes.
+ *  - a cache element's value is its exact e4m3 value times the descale of its (batch, kv head):
+ *    k_descale / v_descale point to fp32 device values read on the device, element
+ *    b * stride[0] + h * stride[1] (a stride of 0 broadcasts); NULL means 1.
+ *  - the score multiplier is (softmax_scale * k_descale) * log2(e) in fp32; v_descale multiplies O
+ *    in fp32 before its one rounding to the output dtype; LSE2 is that of the scaled scores.
+ *  - k_new / v_new (in `dtype`) are quantised on the way in: the byte written is
+ *    e4m3_rne(clamp(float(x) / descale, -448, 448)), the division correctly rounded, NaN kept.
+ *  - head_dim is a multiple of 16 up to 128 and every cache row is 16-byte aligned (pointers and
+ *    strides multiples of 16), else FA2_E_UNSUPPORTED.
+ * Masks, lengths, the append positions, the split count and the workspace are fa2_fwd_kvcache's
+ * (fa2_fwd_kvcache_paged's with a block table). */
+typedef struct fa2_fp8_kvcache_args {
+  fa2_paged_kvcache_args paged;
+  const float* k_descale;       /* device fp32, or NULL (1) */
+  const float* v_descale;
+  int64_t k_descale_stride[2];  /* (batch, kv head) strides in elements; 0 broadcasts */
+  int64_t v_descale_stride[2];
+} fa2_fp8_kvcache_args;
+
+int fa2_fwd_kvcache_fp8(const fa2_fp8_kvcache_args* args, void* stream);
+/* fa2_kvcache_num_splits / fa2_kvcache_workspace_bytes of args->paged.base. */
+int fa2_fp8_kvcache_num_splits(const fa2_fp8_kvcache_args* args);
+int64_t fa2_fp8_kvcache_workspace_bytes(const fa2_fp8_kvcache_args* args);
+
 const char* fa2_last_error(void);
 int fa2_version(void);
 /* Additive revisions of one ABI version (FA2_ABI_VERSION stays what callers compiled against):

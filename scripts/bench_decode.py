@@ -18,8 +18,16 @@ It is timed in the same alternation and reported as paged_over_kvcache[P], next 
 of both variants, which is the margin of that ratio.  --page-order identity leaves the blocks in
 place (table[b, j] = b * max_blocks + j).  Without --page-block-size the output is unchanged.
 
+--fp8 adds an "fp8" variant: flash_attn_with_fp8_kvcache over e4m3 caches of the same shape (random
+bytes of N(0, 1) values, descales 0.5 per (batch, kv head) as device tensors), and with
+--page-block-size a "fp8_paged_pP" variant per P over pools placed by the same kind of table.  They
+are timed in the same alternation and reported as fp8_over_kvcache (and fp8_paged_over_kvcache[P]),
+with fp8_kv_GBps (the fp8 call's K + V bytes, half the 16-bit call's, over its time) and its
+fraction of the copy bandwidth; round_spread of both variants is the margin of the ratio.
+
 usage: python scripts/bench_decode.py [--rounds N] [--iters N] [--hbm-copy-bin PATH | --copy-gbps X]
-                                      [--page-block-size P [P ...]] [--page-order shuffled|identity] [--out FILE]
+                                      [--page-block-size P [P ...]] [--page-order shuffled|identity] [--fp8]
+                                      [--out FILE]
 """
 import argparse
 import ctypes
@@ -33,7 +41,8 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from fa2_triton_amd import _lib as L  # noqa: E402
-from fa2_triton_amd import flash_attn_func, flash_attn_with_kvcache, flash_attn_with_paged_kvcache  # noqa: E402
+from fa2_triton_amd import (flash_attn_func, flash_attn_with_fp8_kvcache, flash_attn_with_kvcache,  # noqa: E402
+                            flash_attn_with_paged_kvcache)
 
 SHAPES = ((1, 8192), (1, 131072), (8, 32768), (64, 8192))
 HQ, HKV, D = 32, 8, 128
@@ -89,6 +98,7 @@ def main(argv=None):
     ap.add_argument("--copy-gbps", type=float, default=None)
     ap.add_argument("--page-block-size", type=int, nargs="+", default=[])
     ap.add_argument("--page-order", choices=("shuffled", "identity"), default="shuffled")
+    ap.add_argument("--fp8", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args(argv)
     copy_gbps = measured_copy_gbps(args.hbm_copy_bin) if args.hbm_copy_bin else args.copy_gbps
@@ -107,6 +117,17 @@ def main(argv=None):
             kp, vp, table = paged_copy(kc, vc, page, args.page_order)
             variants[f"paged_p{page}"] = (lambda kp=kp, vp=vp, table=table:
                                           flash_attn_with_paged_kvcache(q, kp, vp, table, cap))
+        if args.fp8:
+            # byte caches (uint8 for the scatter, viewed as e4m3 for the call) and device descales
+            k8 = torch.empty(batch, cap, HKV, D, device="cuda").normal_().to(torch.float8_e4m3fn).view(torch.uint8)
+            v8 = torch.empty(batch, cap, HKV, D, device="cuda").normal_().to(torch.float8_e4m3fn).view(torch.uint8)
+            kd, vd = torch.full((batch, HKV), 0.5, device="cuda"), torch.full((batch, HKV), 0.5, device="cuda")
+            f8 = lambda t: t.view(torch.float8_e4m3fn)
+            variants["fp8"] = lambda: flash_attn_with_fp8_kvcache(q, f8(k8), f8(v8), kd, vd)
+            for page in args.page_block_size:
+                kp8, vp8, table8 = paged_copy(k8, v8, page, args.page_order)
+                variants[f"fp8_paged_p{page}"] = (lambda kp=kp8, vp=vp8, table=table8: flash_attn_with_fp8_kvcache(
+                    q, f8(kp), f8(vp), kd, vd, block_table=table, cache_seqlens=cap))
         samples = {n: [] for n in variants}
         with torch.no_grad():
             for fn in variants.values():
@@ -133,13 +154,31 @@ def main(argv=None):
             "kv_GBps": round(gbps, 1),
             "frac_of_copy_bandwidth": round(gbps / copy_gbps, 4) if copy_gbps else None,
         })
+        if args.fp8:
+            ref8 = variants["fp8"]()
+            for page in args.page_block_size:
+                if not torch.equal(variants[f"fp8_paged_p{page}"](), ref8):
+                    raise SystemExit(f"fp8 paged P={page} differs from the contiguous fp8 result at B={batch} L={cap}")
+            gbps8 = kv_bytes / 2 / (ms["fp8"] * 1e-3) / 1e9
+            shapes[-1].update({
+                "fp8_over_kvcache": round(ms["fp8"] / ms["kvcache"], 4), "fp8_kv_bytes": kv_bytes // 2,
+                "fp8_fits_last_level_cache": kv_bytes // 2 < LLC_BYTES, "fp8_kv_GBps": round(gbps8, 1),
+                "fp8_frac_of_copy_bandwidth": round(gbps8 / copy_gbps, 4) if copy_gbps else None,
+            })
+            if args.page_block_size:
+                shapes[-1]["fp8_paged_over_kvcache"] = {str(p): round(ms[f"fp8_paged_p{p}"] / ms["kvcache"], 4)
+                                                        for p in args.page_block_size}
         if args.page_block_size:
             shapes[-1]["paged_over_kvcache"] = {str(p): round(ms[f"paged_p{p}"] / ms["kvcache"], 4)
                                                 for p in args.page_block_size}
         del q, kc, vc, variants
+        if args.fp8:
+            del k8, v8
         torch.cuda.empty_cache()
     result = {"bench": "decode", "device": torch.cuda.get_device_name(0), "dtype": "bf16", "Hq": HQ, "Hkv": HKV, "D": D,
               "Sq": 1, "rounds": args.rounds, "iters": args.iters, "copy_GBps": copy_gbps, "shapes": shapes}
+    if args.fp8:
+        result["fp8"] = {"cache_dtype": "float8_e4m3fn", "descales": "0.5 per (batch, kv head), device tensors"}
     if args.page_block_size:
         result["page_block_sizes"], result["page_order"] = args.page_block_size, args.page_order
     line = json.dumps(result)
