@@ -174,6 +174,21 @@ def test_bitwise_equal_to_the_16_bit_call_on_the_upcast_cache(case, dtype):
 
 
 # ---------------------------------------------------------------------------------------------
+def _check_dequantised(q, kf, vf, lens, out, lse, ref, pt, causal, window):
+    """The project's rule for an fp8 call with general descales (2 x the low-precision oracle's error
+    + 5e-5, no escape taken) against the oracle outputs `ref`, `pt` on the dequantised kf, vf, and
+    LSE2 as tests/test_kvcache.py.  (shared with tests/test_kvcache_layouts.py)"""
+    before = dict(tolerance.ESCAPES)
+    report = check_fa_tolerance(q, kf, vf, None, out, ref, pt, out_error_mul=2, out_error_bias=5e-5)
+    print({key: f"{val:.3e}" for key, val in report.items()})
+    assert tolerance.ESCAPES["ulp"] == before["ulp"] and tolerance.ESCAPES["dv_sum"] == before["dv_sum"], report
+    assert out.dtype == q.dtype and torch.isfinite(out).all()
+    want = _lse2(q, kf, lens, causal, window)
+    finite = torch.isfinite(want)
+    assert torch.allclose(lse[finite], want[finite], rtol=1e-3, atol=1e-3), (lse[finite] - want[finite]).abs().max()
+    assert torch.all(torch.isneginf(lse[~finite]))
+
+
 @DTYPES
 @pytest.mark.parametrize("case", ["gqa-32x8-splits4", "two-row-tiles-causal", "d96", "window-30-10-sq4"])
 def test_general_descales_against_the_oracle(case, dtype):
@@ -197,15 +212,7 @@ def test_general_descales_against_the_oracle(case, dtype):
             out, lse = flash_attn_with_fp8_kvcache(q, f8(kp), f8(vp), kd, vd, block_table=table, **kw)
         else:
             out, lse = flash_attn_with_fp8_kvcache(q, f8(k8), f8(v8), kd, vd, **kw)
-        before = dict(tolerance.ESCAPES)
-        report = check_fa_tolerance(q, kf, vf, None, out, ref, pt, out_error_mul=2, out_error_bias=5e-5)
-        print({key: f"{val:.3e}" for key, val in report.items()})
-        assert tolerance.ESCAPES["ulp"] == before["ulp"] and tolerance.ESCAPES["dv_sum"] == before["dv_sum"], report
-        assert out.dtype == dtype and torch.isfinite(out).all()
-        want = _lse2(q, kf, lens, causal, window)
-        finite = torch.isfinite(want)
-        assert torch.allclose(lse[finite], want[finite], rtol=1e-3, atol=1e-3), (lse[finite] - want[finite]).abs().max()
-        assert torch.all(torch.isneginf(lse[~finite]))
+        _check_dequantised(q, kf, vf, lens, out, lse, ref, pt, causal, window)
 
 
 # ---------------------------------------------------------------------------------------------
