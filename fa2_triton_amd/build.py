@@ -45,10 +45,10 @@ UNITS = (
     ("kvcache", "kvcache_kernel.h", ("launch_kvcache_split<{bf}, {dt}>(const fa2_kvcache_args&, int, hipStream_t)",)),
     ("kvcache_paged", "kvcache_kernel.h",
      ("launch_kvcache_split<{bf}, {dt}>(const fa2_paged_kvcache_args&, int, hipStream_t)",)),
-    ("kvcache_fp8", "kvcache_fp8_kernel.h",
-     ("launch_kvcache_fp8_split<{bf}, {dt}, false>(const fa2_fp8_kvcache_args&, int, hipStream_t)",), FP8_TILES),
-    ("kvcache_fp8_paged", "kvcache_fp8_kernel.h",
-     ("launch_kvcache_fp8_split<{bf}, {dt}, true>(const fa2_fp8_kvcache_args&, int, hipStream_t)",), FP8_TILES),
+    ("kvcache_fp8", "kvcache_kernel.h",
+     ("launch_kvcache_split<{bf}, {dt}, fa2_fp8_kvcache_args, false>(const fa2_fp8_kvcache_args&, int, hipStream_t)",), FP8_TILES),
+    ("kvcache_fp8_paged", "kvcache_kernel.h",
+     ("launch_kvcache_split<{bf}, {dt}, fa2_fp8_kvcache_args, true>(const fa2_fp8_kvcache_args&, int, hipStream_t)",), FP8_TILES),
 )
 
 

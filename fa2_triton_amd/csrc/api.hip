@@ -113,7 +113,7 @@ int check_policy(const fa2_policy* p) {
 // k_cache / v_cache with block, row and head strides): pointers, the new rows, 16-byte rows, the
 // workspace and the grid.  On success *nsplit_out is the split count of the call.
 // fp8: the caches hold bytes (fa2_fwd_kvcache_fp8): head_dim a multiple of 16 and cache strides of 16.
-int kvcache_check_call(const fa2_kvcache_args* a, int* nsplit_out, bool fp8 = false) {
+int kvcache_check_call(const fa2_kvcache_args* a, int* nsplit_out, bool fp8) {
   if (!a->q || !a->k_cache || !a->v_cache || !a->o) return fail(FA2_E_INVALID, "null tensor pointer");
   if ((a->k_new != nullptr) != (a->v_new != nullptr)) return fail(FA2_E_INVALID, "k_new and v_new must be given together");
   if (a->k_new ? a->seqlen_new < 1 : a->seqlen_new != 0)
@@ -139,18 +139,26 @@ int kvcache_check_call(const fa2_kvcache_args* a, int* nsplit_out, bool fp8 = fa
   return FA2_OK;
 }
 
-// A call of either layout (Args = fa2_kvcache_args or fa2_paged_kvcache_args, its sizes checked):
-// the shared checks, then the append, the split kernel and the combination.
+// A decode call (Args = fa2_kvcache_args, fa2_paged_kvcache_args or fa2_fp8_kvcache_args, its sizes
+// and what only its entry point checks done): the shared checks, then the append, the split kernel
+// and the combination.  fp8 caches have kernels of their own tiles, per layout.
 template <typename Args>
 int run_kvcache(const Args& args, const char* entry, void* stream) {
+  constexpr bool fp8 = std::is_same_v<Args, fa2_fp8_kvcache_args>;
   const fa2_kvcache_args& a = fa2::kv_base(args);
   int nsplit = 1;
-  if (int rc = kvcache_check_call(&a, &nsplit)) return rc;
+  if (int rc = kvcache_check_call(&a, &nsplit, fp8)) return rc;
   hipStream_t st = (hipStream_t)stream;
   if (a.k_new)
     if (int rc = hip_status(fa2::launch_kvcache_append(args, st), entry, "append launch")) return rc;
-  const hipError_t e = fa2::dispatch([&](auto bf, auto dt) { return fa2::launch_kvcache_split<bf.value, dt.value>(args, nsplit, st); },
-                                     a.dtype == FA2_BF16, fa2::dtypes{}, head_dim_tile(a.head_dim), fa2::tiles{});
+  hipError_t e;
+  if constexpr (fp8)
+    e = fa2::dispatch(
+        [&](auto bf, auto dt, auto paged) { return fa2::launch_kvcache_split<bf.value, dt.value, Args, paged.value>(args, nsplit, st); },
+        a.dtype == FA2_BF16, fa2::dtypes{}, fa2::fp8_head_dim_tile(a.head_dim), fa2::fp8_tiles{}, fa2::fp8_paged(args), fa2::bools{});
+  else
+    e = fa2::dispatch([&](auto bf, auto dt) { return fa2::launch_kvcache_split<bf.value, dt.value>(args, nsplit, st); },
+                      a.dtype == FA2_BF16, fa2::dtypes{}, head_dim_tile(a.head_dim), fa2::tiles{});
   if (int rc = hip_status(e, entry, "launch")) return rc;
   if (nsplit > 1) return hip_status(fa2::launch_kvcache_combine(a, nsplit, st), entry, "combine launch");
   return FA2_OK;
@@ -177,21 +185,12 @@ int fp8_kvcache_check_sizes(const fa2_fp8_kvcache_args* a) {
   return FA2_OK;
 }
 
-// The fp8 call (its sizes checked): run_kvcache's steps with the fp8 kernels; the combination is
-// the 16-bit call's.
-int run_fp8_kvcache(const fa2_fp8_kvcache_args& args, void* stream) {
-  const fa2_kvcache_args& a = args.paged.base;
-  int nsplit = 1;
-  if (int rc = kvcache_check_call(&a, &nsplit, true)) return rc;
-  const char* entry = "fa2_fwd_kvcache_fp8";
-  hipStream_t st = (hipStream_t)stream;
-  if (a.k_new)
-    if (int rc = hip_status(fa2::launch_kvcache_fp8_append(args, st), entry, "append launch")) return rc;
-  const hipError_t e = fa2::dispatch(
-      [&](auto bf, auto dt, auto paged) { return fa2::launch_kvcache_fp8_split<bf.value, dt.value, paged.value>(args, nsplit, st); },
-      a.dtype == FA2_BF16, fa2::dtypes{}, fa2::fp8_head_dim_tile(a.head_dim), fa2::fp8_tiles{}, fa2::fp8_paged(args), fa2::bools{});
-  if (int rc = hip_status(e, entry, "launch")) return rc;
-  if (nsplit > 1) return hip_status(fa2::launch_kvcache_combine(a, nsplit, st), entry, "combine launch");
+// A block table's rows hold the max_blocks = capacity / page_block_size entries a batch can address.
+int check_table_stride(const fa2_paged_kvcache_args* a) {
+  const int64_t max_blocks = a->base.capacity / a->page_block_size;
+  if (a->block_table_stride < max_blocks)
+    return fail(FA2_E_INVALID, "block_table_stride %lld < max_blocks %lld (capacity / page_block_size)",
+                (long long)a->block_table_stride, (long long)max_blocks);
   return FA2_OK;
 }
 }  // namespace
@@ -335,10 +334,7 @@ int fa2_fwd_kvcache_paged(const fa2_paged_kvcache_args* a, void* stream) {
   if (!a) return fail(FA2_E_INVALID, "null args");
   if (int rc = paged_kvcache_check_sizes(a)) return rc;
   if (!a->block_table) return fail(FA2_E_INVALID, "null block_table");
-  const int64_t max_blocks = a->base.capacity / a->page_block_size;
-  if (a->block_table_stride < max_blocks)
-    return fail(FA2_E_INVALID, "block_table_stride %lld < max_blocks %lld (capacity / page_block_size)",
-                (long long)a->block_table_stride, (long long)max_blocks);
+  if (int rc = check_table_stride(a)) return rc;
   return run_kvcache(*a, "fa2_fwd_kvcache_paged", stream);
 }
 
@@ -356,17 +352,12 @@ int fa2_fwd_kvcache_fp8(const fa2_fp8_kvcache_args* args, void* stream) {
   touch_thread_state();
   if (!args) return fail(FA2_E_INVALID, "null args");
   if (int rc = fp8_kvcache_check_sizes(args)) return rc;
-  const fa2_kvcache_args& a = args->paged.base;
-  if (fa2::fp8_paged(*args)) {
-    const int64_t max_blocks = a.capacity / args->paged.page_block_size;
-    if (args->paged.block_table_stride < max_blocks)
-      return fail(FA2_E_INVALID, "block_table_stride %lld < max_blocks %lld (capacity / page_block_size)",
-                  (long long)args->paged.block_table_stride, (long long)max_blocks);
-  }
+  if (fa2::fp8_paged(*args))
+    if (int rc = check_table_stride(&args->paged)) return rc;
   if (((uintptr_t)args->k_descale | (uintptr_t)args->v_descale) & 3) return fail(FA2_E_INVALID, "k_descale / v_descale must be 4-byte aligned");
   for (const int64_t* s : {args->k_descale_stride, args->v_descale_stride})
     if (s[0] < 0 || s[1] < 0) return fail(FA2_E_INVALID, "negative descale stride (%lld, %lld)", (long long)s[0], (long long)s[1]);
-  return run_fp8_kvcache(*args, stream);
+  return run_kvcache(*args, "fa2_fwd_kvcache_fp8", stream);
 }
 
 #if FA2_HP_STAMPS

@@ -80,22 +80,19 @@ hipError_t launch_cu_seqlens(const uint8_t* mask, int64_t stride, int batch, int
 uint32_t dropout_keep_threshold(float p);
 hipError_t launch_dropout_mask(const fa2_fwd_args& a, hipStream_t st);
 
-// KV-cache decode over either cache layout, Args = fa2_kvcache_args or fa2_paged_kvcache_args:
-// the split attention kernel (kvcache_kernel.h, one translation unit per layout, dtype and
-// head-dim tile), the append of k_new / v_new and the combination of nsplit > 1 partial results
-// (kvcache.hip).
-template <bool BF16, int DT, typename Args>
+// KV-cache decode, Args = fa2_kvcache_args, fa2_paged_kvcache_args or fa2_fp8_kvcache_args (DESIGN
+// 12 - 14): the split attention kernel (kvcache_kernel.h, one translation unit per cache type,
+// layout, dtype and head-dim tile; fp8 caches: the tiles of fp8_tiles, and PAGED chosen by the
+// caller from fp8_paged, since one struct serves both layouts), the append of k_new / v_new
+// (kvcache.hip; the quantising one of fp8 caches in kvcache_fp8.hip) and the combination of
+// nsplit > 1 partial results (kvcache.hip), which is the same for all three.
+using fp8_tiles = values<64, 128>;  // DT (fp8_head_dim_tile)
+template <bool BF16, int DT, typename Args, bool PAGED = std::is_same_v<Args, fa2_paged_kvcache_args>>
 hipError_t launch_kvcache_split(const Args& a, int nsplit, hipStream_t st);
 template <typename Args>
 hipError_t launch_kvcache_append(const Args& a, hipStream_t st);
+template <>
+hipError_t launch_kvcache_append(const fa2_fp8_kvcache_args& a, hipStream_t st);
 hipError_t launch_kvcache_combine(const fa2_kvcache_args& a, int nsplit, hipStream_t st);
-
-// The same over fp8 caches (fa2_fp8_kvcache_args): the split kernel
-// (kvcache_fp8_kernel.h, one translation unit per layout, dtype and head-dim tile of fp8_tiles) and
-// the quantising append (kvcache_fp8.hip).  The combination is launch_kvcache_combine.
-using fp8_tiles = values<64, 128>;  // DT (fp8_head_dim_tile)
-template <bool BF16, int DT, bool PAGED>
-hipError_t launch_kvcache_fp8_split(const fa2_fp8_kvcache_args& a, int nsplit, hipStream_t st);
-hipError_t launch_kvcache_fp8_append(const fa2_fp8_kvcache_args& a, hipStream_t st);
 
 }  // namespace fa2

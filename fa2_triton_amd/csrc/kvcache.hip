@@ -1,34 +1,15 @@
 // kvcache.hip -- the small kernels around kvcache_split_kernel (kvcache_kernel.h): the append of
 // new key / value rows to the cache and the combination of the key splits' partial results.
-#include "common.h"
-#include "fa2_internal.h"
+#include "kvcache_kernel.h"
 
 namespace fa2 {
 
-// One thread per 16-byte chunk of a new row: k_new[b, n, h] -> logical row L_b + n of batch b's
-// cache (and V), with L_b = cache_seqlens[b] clamped to [0, capacity] on the device.  A row whose
-// position is at or past the capacity is dropped, so whatever cache_seqlens holds, only rows
-// [0, capacity) of a batch are written.  (dtype-blind: 16-bit elements moved as raw bits.)
-// `where(b, pos, slab, row)` is the layout: logical row pos of batch b is row `row` of slab `slab`
-// (the index of the caches' first stride).
-template <typename Where>
-FA2_DEV void kvcache_append_rows(const fa2_kvcache_args& p, Where where) {
-  const int chunks = p.head_dim >> 3;
-  const int64_t total = (int64_t)p.batch * p.seqlen_new * p.heads_kv * chunks;
-  int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= total) return;
-  const int c = (int)(idx % chunks);
-  idx /= chunks;
-  const int h = (int)(idx % p.heads_kv);
-  idx /= p.heads_kv;
-  const int n = (int)(idx % p.seqlen_new), b = (int)(idx / p.seqlen_new);
-  int L = p.cache_seqlens ? p.cache_seqlens[b] : p.capacity;
-  L = min(max(L, 0), p.capacity);
-  const int64_t pos = (int64_t)L + n;
-  if (pos >= p.capacity) return;
-  int slab;
-  int64_t row;
-  where(b, pos, slab, row);
+// One thread per 16-byte chunk of a new row: k_new[b, n, h] -> row `row` of slab `slab` of the
+// cache (kvcache_append_pos.h), and V likewise.  (dtype-blind: 16-bit elements moved as raw bits.)
+template <bool PAGED, typename Pages>
+FA2_DEV void kvcache_append_rows(const fa2_kvcache_args& p, const Pages& pg) {
+  constexpr int CW = 8;
+#include "kvcache_append_pos.h"
   const uint16_t* ks = (const uint16_t*)p.k_new + b * p.k_new_stride[0] + n * p.k_new_stride[1] + h * p.k_new_stride[2] + 8 * c;
   const uint16_t* vs = (const uint16_t*)p.v_new + b * p.v_new_stride[0] + n * p.v_new_stride[1] + h * p.v_new_stride[2] + 8 * c;
   uint16_t* kd = (uint16_t*)p.k_cache + slab * p.k_cache_stride[0] + row * p.k_cache_stride[1] + h * p.k_cache_stride[2] + 8 * c;
@@ -38,25 +19,9 @@ FA2_DEV void kvcache_append_rows(const fa2_kvcache_args& p, Where where) {
   *(u32x4*)vd = vv;
 }
 
-// contiguous cache [B, capacity, Hkv, D]: row pos of the batch's own slab
-__global__ void __launch_bounds__(256) kvcache_append_kernel(const fa2_kvcache_args p) {
-  kvcache_append_rows(p, [](int b, int64_t pos, int& slab, int64_t& row) {
-    slab = b;
-    row = pos;
-  });
-}
-
-// paged cache: row pos % P of block block_table[b, pos / P], the entry clamped into
-// [0, num_blocks - 1].  Positions at or past capacity = max_blocks * P were dropped, so only table
-// entries [0, max_blocks) are read and only blocks of the pool are written, whatever cache_seqlens
-// and the table hold.
-__global__ void __launch_bounds__(256) kvcache_paged_append_kernel(const fa2_paged_kvcache_args pp) {
-  kvcache_append_rows(pp.base, [&](int b, int64_t pos, int& slab, int64_t& row) {
-    const int log_p = __builtin_ctz(pp.page_block_size);
-    slab = min(max(pp.block_table[(int64_t)b * pp.block_table_stride + (pos >> log_p)], 0), pp.num_blocks - 1);
-    row = pos & (pp.page_block_size - 1);
-  });
-}
+// contiguous cache [B, capacity, Hkv, D] / pools of blocks behind a block table
+__global__ void __launch_bounds__(256) kvcache_append_kernel(const fa2_kvcache_args p) { kvcache_append_rows<false>(p, KvNoPages{}); }
+__global__ void __launch_bounds__(256) kvcache_paged_append_kernel(const fa2_paged_kvcache_args pp) { kvcache_append_rows<true>(pp.base, pp); }
 
 // Per output row (b, h, i), 64 threads (4 columns each), 4 rows per workgroup:
 //   m = max_s lse_s,  w_s = 2^(lse_s - m),  O = sum_s w_s O_s / sum_s w_s,  LSE2 = m + log2 sum_s w_s

@@ -1,7 +1,7 @@
 // kvcache_fp8.hip -- the quantising append of fa2_fwd_kvcache_fp8: new key / value rows in q's dtype
 // written to an fp8 (OCP e4m3fn) cache as e4m3_rne(clamp(float(x) / d, -448, 448)), d the descale of
 // the row's (batch, kv head).  Positions, dropping at the capacity and the paged route through the
-// clamped table entry are kvcache.hip's.
+// clamped table entry are the 16-bit append's (kvcache_append_pos.h).
 #include "common.h"
 #include "fa2_internal.h"
 
@@ -33,34 +33,14 @@ FA2_DEV u32x4 quantise16(u32x4 a, u32x4 b, float d) {
   return out;
 }
 
-// One thread per 16 elements of a new row (32 bytes read, one 16-byte store per cache):
-// kvcache_append_rows with the quantisation.  PAGED: logical row pos is row pos % P of block
-// block_table[b, pos / P], the entry clamped into [0, num_blocks - 1]; positions at or past the
-// capacity were dropped, so only table entries [0, max_blocks) are read and only rows of the
-// caches are written, whatever cache_seqlens and the table hold.
+// One thread per 16 elements of a new row (32 bytes read, one 16-byte store per cache), placed
+// like the 16-bit append's chunks (kvcache_append_pos.h).
 template <bool BF16, bool PAGED>
 __global__ void __launch_bounds__(256) kvcache_fp8_append_kernel(const fa2_fp8_kvcache_args fa) {
-  const fa2_paged_kvcache_args& pp = fa.paged;
+  const fa2_paged_kvcache_args& pg = fa.paged;
   const fa2_kvcache_args& p = fa.paged.base;
-  const int chunks = p.head_dim >> 4;
-  const int64_t total = (int64_t)p.batch * p.seqlen_new * p.heads_kv * chunks;
-  int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= total) return;
-  const int c = (int)(idx % chunks);
-  idx /= chunks;
-  const int h = (int)(idx % p.heads_kv);
-  idx /= p.heads_kv;
-  const int n = (int)(idx % p.seqlen_new), b = (int)(idx / p.seqlen_new);
-  int L = p.cache_seqlens ? p.cache_seqlens[b] : p.capacity;
-  L = min(max(L, 0), p.capacity);
-  const int64_t pos = (int64_t)L + n;
-  if (pos >= p.capacity) return;
-  int64_t slab = b, row = pos;
-  if constexpr (PAGED) {
-    const int log_p = __builtin_ctz(pp.page_block_size);
-    slab = min(max(pp.block_table[(int64_t)b * pp.block_table_stride + (pos >> log_p)], 0), pp.num_blocks - 1);
-    row = pos & (pp.page_block_size - 1);
-  }
+  constexpr int CW = 16;
+#include "kvcache_append_pos.h"
   const float kd = fa.k_descale ? fa.k_descale[b * fa.k_descale_stride[0] + h * fa.k_descale_stride[1]] : 1.f;
   const float vd = fa.v_descale ? fa.v_descale[b * fa.v_descale_stride[0] + h * fa.v_descale_stride[1]] : 1.f;
   const uint16_t* ks = (const uint16_t*)p.k_new + b * p.k_new_stride[0] + n * p.k_new_stride[1] + h * p.k_new_stride[2] + 16 * c;
@@ -72,7 +52,8 @@ __global__ void __launch_bounds__(256) kvcache_fp8_append_kernel(const fa2_fp8_k
   *(u32x4*)vdst = quantise16<BF16>(v0, v1, vd);
 }
 
-hipError_t launch_kvcache_fp8_append(const fa2_fp8_kvcache_args& args, hipStream_t st) {
+template <>
+hipError_t launch_kvcache_append(const fa2_fp8_kvcache_args& args, hipStream_t st) {
   const fa2_kvcache_args& a = args.paged.base;
   const int64_t total = (int64_t)a.batch * a.seqlen_new * a.heads_kv * (a.head_dim >> 4);
   if (total <= 0) return hipSuccess;

@@ -28,6 +28,28 @@
 // key j of batch b in row j % P of block block_table[b, j / P].  kvcache_paged_split_kernel is the
 // same body (kvcache_kernel_body.h) with PAGED = true: what differs is the source address of a
 // tile's rows (stage_tile_paged) and the lookup of the block ids one step ahead (kv_page_ids).
+//
+// fp8 (OCP e4m3fn) caches (fa2_fwd_kvcache_fp8): kvcache_fp8_split_kernel is the same body
+// with FP8 = true: K / V tiles are staged as bytes and converted to q's dtype in registers.
+//  * A cache element's value is its exact e4m3 value (every finite e4m3 value is a bf16 and an
+//    fp16 value), so the conversion is lossless and the MFMAs are those of the 16-bit kernel.  The
+//    per-(batch, kv head) descales never touch K or V: kd goes into the score multiplier
+//    (softmax_scale * kd) * log2e, vd multiplies O in fp32 before its one rounding (on the split
+//    path the fp32 partials, so kvcache_combine_kernel runs unchanged).
+//  * LDS image: a 64-key x DT-byte tile is the Tile<DT / 2, 64> image of its rows read as DT / 2
+//    16-bit words (byte pairs), so stage_tile / stage_tile_paged stage it as they are: DT / 16
+//    LDS-DMA pieces of 16 bytes = 16 elements per lane.
+//  * K rows: lane (r32, hh) reads the 8 bytes 16 ks + 8 hh .. + 7 of key r32 (ds_read_b64) and
+//    converts them to one 16-byte MFMA fragment.
+//  * V^T: ds_read_b64_tr_b16 on the byte pairs (lds_tr_frag on the 16-bit view).  Lane (r32, h)
+//    then holds the pair (d, d + 1), d = 64 su + 2 r32, of the eight keys of a k-step in the
+//    permuted key order of P; v_perm_b32 separates the even and the odd column, and the two feed two
+//    accumulators: acc[2 su] holds columns 64 su + 2 m, acc[2 su + 1] columns 64 su + 2 m + 1 (m the
+//    accumulator row).  The epilogue interleaves them: registers 4 g4 + e of the two accumulators
+//    are the eight consecutive columns 64 su + 16 g4 + 8 hh + 2 e + parity.
+//  * Bytes in flight: a workgroup's LDS is half the 16-bit kernel's (64 KiB + 1 KiB at DT = 128),
+//    and the kernel is bounded to 256 VGPRs, so two workgroups share a CU: per CU the same K and V
+//    bytes are ahead as in the 16-bit kernel (which fits one).
 #pragma once
 #include "common.h"
 #include "fa2_internal.h"
@@ -41,6 +63,13 @@ struct KvCfg {
   static constexpr int kWave = 2 * kTile;          // a wave's K and V tile (its fp32 O image at the merge)
   static constexpr int kPieces = DT / 8;           // LDS-DMA instructions of one tile, per lane
 };
+template <int DT>
+struct KvFp8Cfg {
+  static constexpr int NW = 4;              // waves per workgroup
+  static constexpr int kTile = 64 * DT;     // bytes of a 64-key K or V tile
+  static constexpr int kWave = 2 * kTile;   // a wave's K and V tile (its fp32 O image at the merge)
+  static constexpr int kPieces = DT / 16;   // LDS-DMA instructions of one tile, per lane
+};
 
 template <int N>
 FA2_DEV void vm_wait_but() {
@@ -48,13 +77,18 @@ FA2_DEV void vm_wait_but() {
 }
 FA2_DEV void lds_wait_all() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 
-// What the shared body (kvcache_kernel_body.h) names `pg`: the paging fields of
-// fa2_paged_kvcache_args in the paged kernel, this empty stand-in in the contiguous one
-// (read only inside `if constexpr (PAGED)`, which the contiguous kernel discards).
+// What the shared body (kvcache_kernel_body.h) names `pg` and `fa`: the paging fields of
+// fa2_paged_kvcache_args and the descales of fa2_fp8_kvcache_args in the kernels that have them,
+// these empty stand-ins in the others (read only inside `if constexpr (PAGED)` / `if constexpr
+// (FP8)`, which those kernels discard: a non-dependent name there is still looked up).
 struct KvNoPages {
   const int32_t* block_table = nullptr;
   int64_t block_table_stride = 0;
   int32_t page_block_size = 64, num_blocks = 1;
+};
+struct KvNoDescales {
+  const float *k_descale = nullptr, *v_descale = nullptr;
+  int64_t k_descale_stride[2] = {0, 0}, v_descale_stride[2] = {0, 0};
 };
 
 // The block ids of the (at most four) pages under the 64-key tile at n0 (a multiple of 64, < L),
@@ -120,28 +154,99 @@ FA2_DEV void stage_tile_paged(char* tile, const uint16_t* g, int64_t block_strid
   }
 }
 
+// two e4m3 bytes (the low or the high half of w) as two elements of q's dtype, exactly
+template <bool BF16>
+FA2_DEV uint32_t fp8x2_to_elem(uint32_t w, bool high) {
+  if constexpr (BF16) {
+    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+    const bf16x2 r = high ? __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, true) : __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, false);
+    return __builtin_bit_cast(uint32_t, r);
+  } else {
+    typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+    const f16x2 r = high ? __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w, 1.0f, true) : __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w, 1.0f, false);
+    return __builtin_bit_cast(uint32_t, r);
+  }
+}
+template <bool BF16>
+FA2_DEV u32x4 fp8x8_to_frag(uint32_t lo, uint32_t hi) {
+  return u32x4{fp8x2_to_elem<BF16>(lo, false), fp8x2_to_elem<BF16>(lo, true), fp8x2_to_elem<BF16>(hi, false),
+               fp8x2_to_elem<BF16>(hi, true)};
+}
+
+// K fragment of k-step ks of a byte tile (DH = DT / 2 its width in byte pairs): bytes
+// 16 ks + 8 hh .. + 7 of tile row row0 + r32 (chunk ks of the row, its half hh), converted.
+template <bool BF16, int DH>
+FA2_DEV u32x4 lds_row_frag_fp8(const char* tile, int row0, int r32, int ks, int hh) {
+  const int off = (ks >> 2) * Tile<DH, 64>::kSub + (row0 + r32) * 64 + (((ks & 3) ^ ((r32 >> 2) & 3)) << 4) + 8 * hh;
+  const u32x2 w = *(const u32x2*)(tile + off);
+  return fp8x8_to_frag<BF16>(w[0], w[1]);
+}
+
+// V^T fragments of keys row0 .. row0 + 15 (the permuted order of lds_tr_frag) for the byte pair
+// (64 su + 2 r32, + 1): `even` and `odd` are the two columns' A operands.
+template <bool BF16, int DH>
+FA2_DEV void lds_tr_frag_fp8(u32x4& even, u32x4& odd, const char* tile, int row0, int su, int lane) {
+  const u32x4 t = lds_tr_frag<DH, 64>(tile, row0, 32 * su, lane);  // dword i: keys 2 i, 2 i + 1 as (even, odd) bytes
+  const uint32_t e0 = __builtin_amdgcn_perm(t[1], t[0], 0x06040200u), e1 = __builtin_amdgcn_perm(t[3], t[2], 0x06040200u);
+  const uint32_t o0 = __builtin_amdgcn_perm(t[1], t[0], 0x07050301u), o1 = __builtin_amdgcn_perm(t[3], t[2], 0x07050301u);
+  even = fp8x8_to_frag<BF16>(e0, e1);
+  odd = fp8x8_to_frag<BF16>(o0, o1);
+}
+
+// The body's two choices by cache type.  kv_stage_tile: a 64-key tile through either layout; the
+// overload for a byte cache stages the byte-pair view with the 16-bit stagers (strides and D
+// halved: 16-byte aligned rows make every stride even).  kv_k_frag: the K fragment of k-step ks.
+template <int DT, bool PAGED>
+FA2_DEV void kv_stage_tile(char* tile, const uint16_t* g, int64_t block_stride, int64_t row_stride, int e0, int e1, int e2, int e3,
+                           int log_p, int n0, int L, int D, int lane) {
+  if constexpr (PAGED) stage_tile_paged<DT>(tile, g, block_stride, row_stride, e0, e1, e2, e3, log_p, n0, L, D, lane);
+  else stage_tile<DT, 64, 64, true>(tile, g, row_stride, n0, L, D, lane);
+}
+template <int DT, bool PAGED>
+FA2_DEV void kv_stage_tile(char* tile, const uint8_t* g, int64_t block_stride, int64_t row_stride, int e0, int e1, int e2, int e3,
+                           int log_p, int n0, int L, int D, int lane) {
+  kv_stage_tile<DT / 2, PAGED>(tile, (const uint16_t*)g, block_stride >> 1, row_stride >> 1, e0, e1, e2, e3, log_p, n0, L, D >> 1, lane);
+}
+template <bool BF16, int DT, bool FP8>
+FA2_DEV u32x4 kv_k_frag(const char* tile, int row0, int r32, int ks, int hh) {
+  if constexpr (FP8) return lds_row_frag_fp8<BF16, DT / 2>(tile, row0, r32, ks, hh);
+  else return lds_row_frag<DT, 64>(tile, row0, r32, ks, hh);
+}
+
 template <bool BF16, int DT>
 __global__ void __launch_bounds__(KvCfg<DT>::NW * 64) kvcache_split_kernel(const fa2_kvcache_args p, const int nsplit) {
-  constexpr bool PAGED = false;
+  constexpr bool PAGED = false, FP8 = false;
   constexpr KvNoPages pg{};
+  constexpr KvNoDescales fa{};
 #include "kvcache_kernel_body.h"
 }
 
 template <bool BF16, int DT>
 __global__ void __launch_bounds__(KvCfg<DT>::NW * 64) kvcache_paged_split_kernel(const fa2_paged_kvcache_args pg, const int nsplit) {
-  constexpr bool PAGED = true;
+  constexpr bool PAGED = true, FP8 = false;
+  constexpr KvNoDescales fa{};
   const fa2_kvcache_args& p = pg.base;
 #include "kvcache_kernel_body.h"
 }
 
-// One launcher for both layouts: the kernel follows from the argument struct.
-template <bool BF16, int DT, typename Args>
+// 256 threads, two workgroups per CU (at most 256 VGPRs): see "bytes in flight" above
+template <bool BF16, int DT, bool PAGED>
+__global__ void __launch_bounds__(256, 2) kvcache_fp8_split_kernel(const fa2_fp8_kvcache_args fa, const int nsplit) {
+  constexpr bool FP8 = true;
+  const fa2_paged_kvcache_args& pg = fa.paged;
+  const fa2_kvcache_args& p = fa.paged.base;
+#include "kvcache_kernel_body.h"
+}
+
+// One launcher for the three argument structs: the kernel follows from the struct and, for fp8
+// caches (one struct for both layouts), from PAGED (fa2_internal.h has its default).
+template <bool BF16, int DT, typename Args, bool PAGED>
 hipError_t launch_kvcache_split(const Args& a, int nsplit, hipStream_t st) {
-  const dim3 grid((unsigned)(kv_units(kv_base(a)) * nsplit)), block(KvCfg<DT>::NW * 64);
-  if constexpr (std::is_same_v<Args, fa2_paged_kvcache_args>)
-    hipLaunchKernelGGL((kvcache_paged_split_kernel<BF16, DT>), grid, block, 0, st, a, nsplit);
-  else
-    hipLaunchKernelGGL((kvcache_split_kernel<BF16, DT>), grid, block, 0, st, a, nsplit);
+  constexpr bool FP8 = std::is_same_v<Args, fa2_fp8_kvcache_args>;
+  const dim3 grid((unsigned)(kv_units(kv_base(a)) * nsplit)), block(std::conditional_t<FP8, KvFp8Cfg<DT>, KvCfg<DT>>::NW * 64);
+  if constexpr (FP8) hipLaunchKernelGGL((kvcache_fp8_split_kernel<BF16, DT, PAGED>), grid, block, 0, st, a, nsplit);
+  else if constexpr (PAGED) hipLaunchKernelGGL((kvcache_paged_split_kernel<BF16, DT>), grid, block, 0, st, a, nsplit);
+  else hipLaunchKernelGGL((kvcache_split_kernel<BF16, DT>), grid, block, 0, st, a, nsplit);
   return hipGetLastError();
 }
 

@@ -193,9 +193,10 @@ inline BwdPlan select_bwd(const fa2_bwd_args& a, bool aligned, int stages, const
 // ---------------------------------------------------------------------------------------------
 // KV-cache decode (kvcache_kernel.h): the unit count, the split heuristic and the workspace size.
 // Functions of the shapes only -- never of the cache lengths, which stay on the device.  A paged
-// call uses those of its `base`.
+// call uses those of its `base`, an fp8 call those of its `paged.base`.
 inline const fa2_kvcache_args& kv_base(const fa2_kvcache_args& a) { return a; }
 inline const fa2_kvcache_args& kv_base(const fa2_paged_kvcache_args& a) { return a.base; }
+inline const fa2_kvcache_args& kv_base(const fa2_fp8_kvcache_args& a) { return a.paged.base; }
 
 // 32-row tiles of a kv head's rows (the Hq / Hkv q-heads of the group x the Sq query positions)
 inline int kv_row_tiles(const fa2_kvcache_args& a) {
@@ -232,7 +233,7 @@ inline int64_t kv_workspace_bytes(const fa2_kvcache_args& a, int nsplit) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// fp8 caches (kvcache_fp8_kernel.h): the kernels exist for the head-dim tiles 64 and 128 (a tile's
+// fp8 caches (kvcache_kernel.h, FP8): the kernels exist for the head-dim tiles 64 and 128 (a tile's
 // rows are DT bytes, 16-byte pieces of 16 elements) and both layouts.  Units, splits and workspace
 // are those of `paged.base` above.
 constexpr int kFp8MaxHeadDim = 128;
