@@ -112,6 +112,33 @@ inline unsigned long long* hp_stamp_buf() {
   return buf;
 }
 #endif
+// The unit loop of the hand-placed dQ and dK/dV kernels between marks: mark(k) adds the cycles
+// since the previous mark (or start) to counter k, count(k) adds one, parts() is store_rows_lds's
+// three counters (9-11), flush adds the wave's sums to the device buffer.  Empty in a shipped
+// build: no register, no instruction.
+struct HpStamps {
+#if FA2_HP_STAMPS
+  uint64_t acc[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  uint64_t t = 0;
+  FA2_DEV void start() { t = __builtin_amdgcn_s_memtime(); }
+  FA2_DEV void mark(int k) {
+    const uint64_t now = __builtin_amdgcn_s_memtime();
+    acc[k] += now - t;
+    t = now;
+  }
+  FA2_DEV void count(int k) { acc[k] += 1; }
+  FA2_DEV uint64_t* parts() { return acc + 9; }
+  FA2_DEV void flush(unsigned long long* out, int lane) {
+    if (lane == 0 && out)
+      for (int k = 0; k < 16; ++k) atomicAdd(out + k, (unsigned long long)acc[k]);
+  }
+#else
+  FA2_DEV void start() {}
+  FA2_DEV void mark(int) {}
+  FA2_DEV void count(int) {}
+  FA2_DEV uint64_t* parts() { return nullptr; }
+#endif
+};
 
 // ---------------------------------------------------------------------------------------------
 // Cross-half exchange: returns {x of lanes 0-31, x of lanes 32-63} in every lane.
