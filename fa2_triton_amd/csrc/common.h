@@ -112,10 +112,10 @@ inline unsigned long long* hp_stamp_buf() {
   return buf;
 }
 #endif
-// The unit loop of the hand-placed dQ and dK/dV kernels between marks: mark(k) adds the cycles
-// since the previous mark (or start) to counter k, count(k) adds one, parts() is store_rows_lds's
-// three counters (9-11), flush adds the wave's sums to the device buffer.  Empty in a shipped
-// build: no register, no instruction.
+// The unit loop of the hand-placed kernels between marks: mark(k) adds the cycles since the
+// previous mark (or start) to counter k, count(k) adds one, add(k, v) a count taken elsewhere (the
+// forward statement's own stamps), parts() is store_rows_lds's three counters (9-11), flush adds
+// the wave's sums to the device buffer.  Empty in a shipped build: no register, no instruction.
 struct HpStamps {
 #if FA2_HP_STAMPS
   uint64_t acc[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -127,6 +127,7 @@ struct HpStamps {
     t = now;
   }
   FA2_DEV void count(int k) { acc[k] += 1; }
+  FA2_DEV void add(int k, uint64_t v) { acc[k] += v; }
   FA2_DEV uint64_t* parts() { return acc + 9; }
   FA2_DEV void flush(unsigned long long* out, int lane) {
     if (lane == 0 && out)
@@ -309,6 +310,16 @@ FA2_DEV u32x4 lds_tr_frag(const char* tile, int row0, int col0, int lane) {
   s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)pb);
   u32x2 a = __builtin_bit_cast(u32x2, lo), b = __builtin_bit_cast(u32x2, hi);
   return u32x4{a[0], a[1], b[0], b[1]};
+}
+
+// The lane part of lds_row_frag's address for the hand-placed statements (fwd_hp, dq_hp, dkdv_hp),
+// which reach every (tile, sub-tile, row block, k-step pair) through ds offset immediates from
+// two bases per lane: row r32 of sub-tile 0, chunk cc = 2 half + hh (half = ks & 1), counted from
+// the LDS address sb.  (The lane parts of lds_tr_frag's two reads, pa and pb at row0 = col0 = 0,
+// are written out in each of those kernels -- va / vb, ta / tb: as a function, in every form
+// tried, they changed the kernels' code.)
+FA2_DEV uint32_t hp_row_frag_base(uint32_t sb, int r32, int hh, int half) {
+  return sb + r32 * 64 + ((((half << 1) | hh) ^ ((r32 >> 2) & 3)) << 4);
 }
 
 // ---------------------------------------------------------------------------------------------

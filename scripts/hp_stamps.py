@@ -55,6 +55,9 @@ def run_one(lib_path, cases):
         periods = tiles / (waves / 4)
         rec = {"lib": os.path.basename(lib_path), "S": S, "B": B, "causal": causal,
                "ms": round(e0.elapsed_time(e1) / reps, 4), "periods_per_unit": round(periods, 2)}
+        # counters (HpStamps in fwd_hp_kernel): 0 - 3 the statement's own stamps, 5 units, 6 read-out,
+        # 7 / 8 the row blocks, 9 - 11 store_rows_lds's parts; the epilogue is 6 + 7 + 8
+        st[4] = st[6] + st[7] + st[8]
         for name, i in (("phase_x", 0), ("phase_y", 1), ("waits", 2), ("statement", 3), ("epilogue", 4)):
             rec[name + "_cyc_per_period"] = round(st[i] / waves / periods, 1)
         rec["rest_cyc_per_unit"] = round((st[3] - st[0] - st[1] - st[2]) / waves, 1)
