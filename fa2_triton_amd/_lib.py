@@ -176,6 +176,16 @@ class Fp8KvCacheArgs(ctypes.Structure):
     ]
 
 
+class PrefixKvCacheArgs(ctypes.Structure):
+    """Mirror of fa2_prefix_kvcache_args (include/fa2_amd.h): the per-sequence call and the shared
+    prefix, each a fa2_paged_kvcache_args (a NULL block_table is the contiguous layout)."""
+
+    _fields_ = [
+        ("seq", PagedKvCacheArgs),
+        ("prefix", PagedKvCacheArgs),
+    ]
+
+
 ABI_VERSION = 10  # FA2_ABI_VERSION in include/fa2_amd.h
 ABI_MINOR = 1  # FA2_ABI_MINOR: additive revisions of ABI 10 (1: the fa2_kvcache_* entry points)
 KVCACHE_MIN_SPLIT_TILES, KVCACHE_MAX_SPLITS = 4, 128  # FA2_KVCACHE_* in include/fa2_amd.h
@@ -185,10 +195,12 @@ EXPORTED_SYMBOLS = ("fa2_fwd", "fa2_fwd_ex", "fa2_bwd", "fa2_bwd_stages", "fa2_b
                     "fa2_last_error", "fa2_version", "fa2_abi_minor", "fa2_fwd_kvcache", "fa2_kvcache_num_splits",
                     "fa2_kvcache_workspace_bytes", "fa2_fwd_kvcache_paged", "fa2_paged_kvcache_num_splits",
                     "fa2_paged_kvcache_workspace_bytes", "fa2_fwd_kvcache_fp8", "fa2_fp8_kvcache_num_splits",
-                    "fa2_fp8_kvcache_workspace_bytes")
+                    "fa2_fp8_kvcache_workspace_bytes", "fa2_fwd_kvcache_prefix", "fa2_prefix_kvcache_num_splits",
+                    "fa2_prefix_kvcache_workspace_bytes")
 # added within ABI 10 minor 1 (the version numbers did not move): detected by the symbol's presence
 PAGED_KVCACHE_SYMBOL = "fa2_fwd_kvcache_paged"
 FP8_KVCACHE_SYMBOL = "fa2_fwd_kvcache_fp8"
+PREFIX_KVCACHE_SYMBOL = "fa2_fwd_kvcache_prefix"
 # fa2_path bits (fa2_policy.disable)
 PATH_FWD_HP, PATH_DQ_HP, PATH_DKDV_HP = 1, 2, 4
 
@@ -242,6 +254,14 @@ def bind(lib: ctypes.CDLL) -> ctypes.CDLL:
         lib.fa2_fp8_kvcache_num_splits.restype = ctypes.c_int
         lib.fa2_fp8_kvcache_workspace_bytes.argtypes = [ctypes.POINTER(Fp8KvCacheArgs)]
         lib.fa2_fp8_kvcache_workspace_bytes.restype = ctypes.c_int64
+    if hasattr(lib, PREFIX_KVCACHE_SYMBOL):  # a library without the shared-prefix entry points is rejected by load()
+        lib.fa2_fwd_kvcache_prefix.argtypes = [ctypes.POINTER(PrefixKvCacheArgs), ctypes.c_void_p]
+        lib.fa2_fwd_kvcache_prefix.restype = ctypes.c_int
+        lib.fa2_prefix_kvcache_num_splits.argtypes = [ctypes.POINTER(PrefixKvCacheArgs), ctypes.POINTER(ctypes.c_int),
+                                                      ctypes.POINTER(ctypes.c_int)]
+        lib.fa2_prefix_kvcache_num_splits.restype = ctypes.c_int
+        lib.fa2_prefix_kvcache_workspace_bytes.argtypes = [ctypes.POINTER(PrefixKvCacheArgs)]
+        lib.fa2_prefix_kvcache_workspace_bytes.restype = ctypes.c_int64
     return lib
 
 
@@ -273,6 +293,10 @@ def load() -> ctypes.CDLL:
         if not hasattr(lib, FP8_KVCACHE_SYMBOL):
             raise RuntimeError(f"fa2_triton_amd: library {LIB_PATH} has no {FP8_KVCACHE_SYMBOL} (the fp8 KV-cache "
                                f"entry points, added within ABI {ABI_VERSION}.{ABI_MINOR}); rebuild it with "
+                               "`python -m fa2_triton_amd.build`")
+        if not hasattr(lib, PREFIX_KVCACHE_SYMBOL):
+            raise RuntimeError(f"fa2_triton_amd: library {LIB_PATH} has no {PREFIX_KVCACHE_SYMBOL} (the shared-prefix "
+                               f"KV-cache entry points, added within ABI {ABI_VERSION}.{ABI_MINOR}); rebuild it with "
                                "`python -m fa2_triton_amd.build`")
         _lib = lib
     return _lib

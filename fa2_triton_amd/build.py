@@ -133,7 +133,8 @@ def build(force: bool = False, jobs: int = 0) -> str:
     os.makedirs(OBJ, exist_ok=True)
     generated_headers()
     srcs = [os.path.join(CSRC, "api.hip"), os.path.join(CSRC, "misc.hip"),
-            os.path.join(CSRC, "kvcache.hip"), os.path.join(CSRC, "kvcache_fp8.hip")] + generated_sources()
+            os.path.join(CSRC, "kvcache.hip"), os.path.join(CSRC, "kvcache_fp8.hip"),
+            os.path.join(CSRC, "kvprefix.hip")] + generated_sources()
     dep_t = deps_mtime()
     jobs = jobs or min(16, os.cpu_count() or 4)
     with ThreadPoolExecutor(max_workers=jobs) as ex:

@@ -193,6 +193,67 @@ int check_table_stride(const fa2_paged_kvcache_args* a) {
                 (long long)a->block_table_stride, (long long)max_blocks);
   return FA2_OK;
 }
+
+// Shared-prefix decode (fa2_fwd_kvcache_prefix): what the call runs, derived from the
+// sizes alone.  `prefix` is the prefix pass as the split kernel of its layout takes it: batch 1,
+// seqlen_q = B * Sq, no mask, no append; `seq` the per-sequence pass with its split count forced.
+// The pointers that depend on the call (q's row stride, the workspace regions) are filled in by
+// fa2_fwd_kvcache_prefix.
+struct PrefixPlan {
+  fa2_paged_kvcache_args prefix, seq;
+  int ns_p, ns_s;
+  int64_t region_p, region_s;  // bytes of the two workspace regions, each a multiple of 16
+};
+
+int check_sizes_of_layout(const fa2_paged_kvcache_args* a) {
+  return a->block_table ? paged_kvcache_check_sizes(a) : kvcache_check_sizes(&a->base);
+}
+
+// a pass always hands over fp32 partials: at least two splits (kvcache_kernel_body.h writes a
+// rounded O with one)
+int prefix_pass_splits(const fa2_kvcache_args& a) {
+  const int n = a.num_splits >= 1 ? a.num_splits : fa2::kv_auto_splits(a, fa2::device_cu_count());
+  return n < 2 ? 2 : n;
+}
+
+int prefix_kvcache_plan(const fa2_prefix_kvcache_args* args, PrefixPlan* plan) {
+  const fa2_kvcache_args& s = args->seq.base;
+  const fa2_kvcache_args& x = args->prefix.base;
+  if (int rc = check_sizes_of_layout(&args->seq)) return rc;
+  if (s.window_left >= 0)
+    return fail(FA2_E_UNSUPPORTED, "window_left=%d: a left window bound is not supported with a shared prefix", s.window_left);
+  if (s.num_splits == 1 || x.num_splits == 1)
+    return fail(FA2_E_INVALID, "num_splits=1 (%s): both passes hand fp32 partial results to the merge, which a pass with one "
+                "split does not write; force 2 .. %d or pass 0", s.num_splits == 1 ? "seq" : "prefix", FA2_KVCACHE_MAX_SPLITS);
+  const bool zero = !x.q && !x.o && !x.lse && !x.k_new && !x.v_new && !x.workspace && !x.workspace_bytes && !x.batch &&
+                    !x.heads_q && !x.heads_kv && !x.seqlen_q && !x.head_dim && !x.seqlen_new && !x.causal && !x.window_left &&
+                    !x.window_right && !x.dtype && x.softmax_scale == 0.f;
+  bool zero_strides = true;
+  for (const int64_t* st : {x.q_stride, x.o_stride, x.k_new_stride, x.v_new_stride})
+    zero_strides = zero_strides && !st[0] && !st[1] && !st[2];
+  if (!zero || !zero_strides)
+    return fail(FA2_E_INVALID, "a field of `prefix` other than the caches, their strides, capacity, cache_seqlens, the paging "
+                "fields and num_splits is not zero");
+  const int64_t rows = (int64_t)s.batch * s.seqlen_q;
+  if (rows > (1 << 24)) return fail(FA2_E_UNSUPPORTED, "batch * seqlen_q = %lld > 2^24", (long long)rows);
+  plan->prefix = args->prefix;
+  fa2_kvcache_args& p = plan->prefix.base;
+  p.batch = 1;
+  p.heads_q = s.heads_q;
+  p.heads_kv = s.heads_kv;
+  p.seqlen_q = (int32_t)rows;
+  p.head_dim = s.head_dim;
+  p.window_left = p.window_right = -1;
+  p.dtype = s.dtype;
+  p.softmax_scale = s.softmax_scale;
+  if (int rc = check_sizes_of_layout(&plan->prefix)) return rc;
+  plan->seq = args->seq;
+  plan->ns_p = p.num_splits = prefix_pass_splits(p);
+  plan->ns_s = plan->seq.base.num_splits = prefix_pass_splits(s);
+  plan->region_p = (fa2::kv_workspace_bytes(p, plan->ns_p) + 15) & ~(int64_t)15;
+  plan->region_s = (fa2::kv_workspace_bytes(s, plan->ns_s) + 15) & ~(int64_t)15;
+  return FA2_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -358,6 +419,78 @@ int fa2_fwd_kvcache_fp8(const fa2_fp8_kvcache_args* args, void* stream) {
   for (const int64_t* s : {args->k_descale_stride, args->v_descale_stride})
     if (s[0] < 0 || s[1] < 0) return fail(FA2_E_INVALID, "negative descale stride (%lld, %lld)", (long long)s[0], (long long)s[1]);
   return run_kvcache(*args, "fa2_fwd_kvcache_fp8", stream);
+}
+
+int fa2_prefix_kvcache_num_splits(const fa2_prefix_kvcache_args* args, int* prefix_splits, int* seq_splits) {
+  PrefixPlan plan;
+  const int rc = args ? prefix_kvcache_plan(args, &plan) : fail(FA2_E_INVALID, "null args");
+  if (prefix_splits) *prefix_splits = rc ? 0 : plan.ns_p;
+  if (seq_splits) *seq_splits = rc ? 0 : plan.ns_s;
+  return rc;
+}
+
+int64_t fa2_prefix_kvcache_workspace_bytes(const fa2_prefix_kvcache_args* args) {
+  PrefixPlan plan;
+  if (!args || prefix_kvcache_plan(args, &plan)) return 0;
+  return plan.region_p + plan.region_s;
+}
+
+int fa2_fwd_kvcache_prefix(const fa2_prefix_kvcache_args* args, void* stream) {
+  touch_thread_state();
+  const char* entry = "fa2_fwd_kvcache_prefix";
+  if (!args) return fail(FA2_E_INVALID, "null args");
+  PrefixPlan plan;
+  if (int rc = prefix_kvcache_plan(args, &plan)) return rc;
+  fa2_kvcache_args& s = plan.seq.base;
+  fa2_kvcache_args& p = plan.prefix.base;
+  for (const fa2_paged_kvcache_args* side : {&plan.seq, &plan.prefix})
+    if (side->block_table)
+      if (int rc = check_table_stride(side)) return rc;
+  // one caller-owned buffer, the prefix region first
+  const int64_t need = plan.region_p + plan.region_s;
+  if (!s.workspace || s.workspace_bytes < need)
+    return fail(FA2_E_INVALID, "workspace_bytes %lld < %lld required for %d prefix + %d sequence splits",
+                (long long)(s.workspace ? s.workspace_bytes : 0), (long long)need, plan.ns_p, plan.ns_s);
+  if (!aligned16(s.workspace)) return fail(FA2_E_INVALID, "workspace must be 16-byte aligned");
+  float* ws_p = (float*)s.workspace;
+  float* ws_s = (float*)((char*)s.workspace + plan.region_p);
+  // the prefix pass reads q as [1, B * Sq, Hq, D]: row b * Sq + i at (b * Sq + i) * row stride
+  int64_t row_stride = s.q_stride[1];
+  if (s.seqlen_q == 1) row_stride = s.q_stride[0];
+  else if (s.batch > 1 && s.q_stride[0] != s.seqlen_q * s.q_stride[1])
+    return fail(FA2_E_UNSUPPORTED, "q_stride[0]=%lld != seqlen_q * q_stride[1]=%lld: q does not collapse to [1, B * Sq, Hq, D]",
+                (long long)s.q_stride[0], (long long)(s.seqlen_q * s.q_stride[1]));
+  p.q = s.q;
+  p.q_stride[0] = row_stride * p.seqlen_q;
+  p.q_stride[1] = row_stride;
+  p.q_stride[2] = s.q_stride[2];
+  p.o = s.o;  // never written: the pass has at least two splits
+  for (int i = 0; i < 3; ++i) p.o_stride[i] = s.o_stride[i];
+  p.workspace = ws_p;
+  p.workspace_bytes = plan.region_p;
+  s.workspace = ws_s;
+  s.workspace_bytes = plan.region_s;
+  // the counts come back as forced: plan.ns_s and plan.ns_p
+  int ns_p = 0, ns_s = 0;
+  if (int rc = kvcache_check_call(&s, &ns_s, false)) return rc;
+  if (int rc = kvcache_check_call(&p, &ns_p, false)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  if (s.k_new) {
+    const hipError_t e = plan.seq.block_table ? fa2::launch_kvcache_append(plan.seq, st) : fa2::launch_kvcache_append(s, st);
+    if (int rc = hip_status(e, entry, "append launch")) return rc;
+  }
+  const auto split_pass = [&](const fa2_paged_kvcache_args& pass, int nsplit) {
+    const fa2_kvcache_args& a = pass.base;
+    return fa2::dispatch(
+        [&](auto bf, auto dt) {
+          if (pass.block_table) return fa2::launch_kvcache_split<bf.value, dt.value>(pass, nsplit, st);
+          return fa2::launch_kvcache_split<bf.value, dt.value>(a, nsplit, st);
+        },
+        a.dtype == FA2_BF16, fa2::dtypes{}, head_dim_tile(a.head_dim), fa2::tiles{});
+  };
+  if (int rc = hip_status(split_pass(plan.prefix, ns_p), entry, "prefix launch")) return rc;
+  if (int rc = hip_status(split_pass(plan.seq, ns_s), entry, "launch")) return rc;
+  return hip_status(fa2::launch_kvprefix_merge(s, ws_p, ns_p, ws_s, ns_s, st), entry, "merge launch");
 }
 
 #if FA2_HP_STAMPS

@@ -94,5 +94,10 @@ hipError_t launch_kvcache_append(const Args& a, hipStream_t st);
 template <>
 hipError_t launch_kvcache_append(const fa2_fp8_kvcache_args& a, hipStream_t st);
 hipError_t launch_kvcache_combine(const fa2_kvcache_args& a, int nsplit, hipStream_t st);
+// Shared-prefix decode (kvprefix.hip): the merge of the prefix pass's ns_p partial results
+// at ws_p ([ns_p, 1, Hq, B * Sq, D] and their LSE2) with the sequence pass's ns_s at ws_s
+// ([ns_s, B, Hq, Sq, D] and theirs) into o / lse of `a`, the per-sequence call.
+hipError_t launch_kvprefix_merge(const fa2_kvcache_args& a, const float* ws_p, int ns_p, const float* ws_s, int ns_s,
+                                 hipStream_t st);
 
 }  // namespace fa2

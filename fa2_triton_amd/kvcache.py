@@ -2,7 +2,9 @@
 over one contiguous cache slab per sequence, and `flash_attn_with_paged_kvcache`
 (`fa2_fwd_kvcache_paged`) over a pool of fixed-size blocks addressed through a block table, and
 `flash_attn_with_fp8_kvcache` (`fa2_fwd_kvcache_fp8`) over caches of either layout that hold
-`float8_e4m3fn` bytes with a descale per (batch, kv head).
+`float8_e4m3fn` bytes with a descale per (batch, kv head), and `flash_attn_with_prefix_kvcache`
+(`fa2_fwd_kvcache_prefix`) over 16-bit caches of either layout behind a prefix that all sequences
+share and that is attended once for the whole batch.
 
 One query token, or a few, per sequence against a pre-allocated key / value cache whose sequences
 have their own filled lengths.  The lengths stay on the device: nothing here reads a tensor's
@@ -249,6 +251,152 @@ def flash_attn_with_paged_kvcache(
     _fill_paging(args, block_table, k_cache)
     return _run(args, args.base, lib.fa2_paged_kvcache_workspace_bytes, lib.fa2_fwd_kvcache_paged, q, k_cache, v_cache,
                 new, seqlens, cap, softmax_scale, causal, left, right, num_splits, return_lse)
+
+
+def _fill_cache_side(side, k_cache, v_cache, block_table, seqlens, cap, num_splits) -> None:
+    """What both sides of a fa2_prefix_kvcache_args state: the caches, their strides, the capacity,
+    the lengths, the paging fields and the split count."""
+    base = side.base
+    base.k_cache, base.v_cache = k_cache.data_ptr(), v_cache.data_ptr()
+    base.k_cache_stride[:] = bshd_strides(k_cache)
+    base.v_cache_stride[:] = bshd_strides(v_cache)
+    base.cache_seqlens = seqlens.data_ptr() if seqlens is not None else None
+    base.capacity, base.num_splits = cap, num_splits
+    if block_table is not None:
+        _fill_paging(side, block_table, k_cache)
+
+
+def flash_attn_with_prefix_kvcache(
+    q: Tensor,
+    prefix_k: Tensor,
+    prefix_v: Tensor,
+    k_cache: Tensor,
+    v_cache: Tensor,
+    prefix_seqlen: Union[None, int, Tensor] = None,
+    cache_seqlens: Union[None, int, Tensor] = None,
+    prefix_block_table: Optional[Tensor] = None,
+    block_table: Optional[Tensor] = None,
+    k: Optional[Tensor] = None,
+    v: Optional[Tensor] = None,
+    softmax_scale: Optional[float] = None,
+    causal: bool = False,
+    window_size: Tuple[int, int] = (-1, -1),
+    num_splits: int = 0,
+    prefix_num_splits: int = 0,
+    return_lse: bool = False,
+):
+    """Shared-prefix (cascade) decode attention: every query of `q` [B, Sq, Hq, D] attends to the
+    first Lp keys of one prefix (`prefix_k` / `prefix_v`) that all batch rows share, and to the keys
+    of its own sequence in `k_cache` / `v_cache` exactly as `flash_attn_with_kvcache` (with
+    `block_table`: `flash_attn_with_paged_kvcache`) would show them; one softmax runs over the union.
+    With every L_b >= Sq that is bottom-right aligned causal attention over the concatenation
+    [prefix[:Lp]; cache_b[:L_b]].
+
+    The prefix is attended once for the whole batch, as B * Sq query positions of one batch row (full
+    32-row tiles in place of B mostly empty ones, and the prefix keys staged once per kv head rather
+    than once per batch row); the two partial results are merged by their log-sum-exp in fp32 and
+    rounded once.  When it pays (bf16, D = 128, Hq = 32, Hkv = 8, Sq = 1, one
+    MI355X, against `flash_attn_with_paged_kvcache` over block tables that alias the prefix blocks):
+    0.58 x the time at B = 64 with a prefix of 75 % of the keys, 0.78 x at B = 8 with 87.5 %, even
+    at B = 64 with 12.5 %, and 1.32 x (slower: one more launch and a workspace round trip) at B = 1.
+    Use it for batches of 8 and more whose shared prefix is the larger part of the keys, never for
+    B = 1.
+
+    Inference only: no autograd graph is built and the result never requires grad.  Not implemented:
+    a left window bound, fp8 caches, more than one prefix level, rotary embedding, bias, dropout,
+    backward.
+
+    prefix_k, prefix_v: [1, cap_p, Hkv, D], or with `prefix_block_table` (int32 [1, max_blocks_p])
+        pools [num_blocks, P, Hkv, D], which may be the very pools of `k_cache` / `v_cache`.
+    prefix_seqlen: Lp: None (cap_p), a Python int, or an int32 device tensor [1] that is read on the
+        device; clamped to [0, cap_p].  It is not modified.
+    k_cache, v_cache, cache_seqlens, block_table: the per-sequence caches, [B, cap, Hkv, D] or, with
+        `block_table` (then `cache_seqlens` is required), pools; the rules of the two functions named
+        above.  The two sides choose their layouts independently.
+    k, v: optional new rows [B, Sn, Hkv, D], appended to the per-sequence caches only.
+    causal, window_size=(left, right): apply to the keys of the sequence, bottom-right aligned on L_b
+        as in `flash_attn_with_kvcache`; every prefix key is always visible.  `left` must be negative
+        (NotImplementedError otherwise).  A row that sees no key at all (Lp = 0 and no visible key of
+        its own) gives 0 and an LSE of -inf.
+    num_splits, prefix_num_splits: the key splits of the per-sequence pass and of the prefix pass:
+        0 lets the library choose (at least 2), 2 .. 128 forces the count.  1 is rejected: both passes
+        hand fp32 partial results to the merge, which a pass with one split does not write.
+    return_lse: also return the base-2 log-sum-exp [B, Hq, Sq] in fp32.
+
+    q must collapse to [1, B * Sq, Hq, D]: with Sq == 1 any batch stride does (a slice of a fused QKV
+    buffer needs no copy), otherwise a q with `q.stride(0) != Sq * q.stride(1)` is copied first.
+
+    Returns `out` [B, Sq, Hq, D] in q's dtype, or `(out, lse)`.
+    """
+    paged, prefix_paged = block_table is not None, prefix_block_table is not None
+    if paged and cache_seqlens is None:
+        raise TypeError("cache_seqlens is required with a paged cache: an int or an int32 tensor")
+    left, right = _check_plain_args(k, v, window_size, num_splits, cache_seqlens)
+    if not isinstance(prefix_num_splits, int) or isinstance(prefix_num_splits, bool) or not 0 <= prefix_num_splits <= MAX_SPLITS:
+        raise ValueError(f"prefix_num_splits must be an int in 0 .. {MAX_SPLITS}, got {prefix_num_splits!r}")
+    if isinstance(prefix_seqlen, bool) or not (prefix_seqlen is None or isinstance(prefix_seqlen, (int, Tensor))):
+        raise TypeError(f"prefix_seqlen must be None, an int or an int32 tensor, got {type(prefix_seqlen).__name__}")
+    if left >= 0:
+        raise NotImplementedError(f"window_size[0] = {left}: a left window bound is not supported with a shared prefix")
+    for name, n in (("num_splits", num_splits), ("prefix_num_splits", prefix_num_splits)):
+        if n == 1:
+            raise ValueError(f"{name} = 1: both passes hand fp32 partial results to the merge, which a pass with one split "
+                             f"does not write; pass 0 or 2 .. {MAX_SPLITS}")
+    for name, t in (("prefix_k", prefix_k), ("prefix_v", prefix_v), ("k_cache", k_cache), ("v_cache", v_cache)):
+        if isinstance(t, Tensor) and str(t.dtype).startswith("torch.float8"):
+            raise NotImplementedError(f"{name} is {t.dtype}: fp8 caches are not supported with a shared prefix")
+    for name, t in (("block_table", block_table), ("prefix_block_table", prefix_block_table)):
+        if t is not None and (not isinstance(t, Tensor) or t.dim() != 2):
+            raise ValueError(f"{name} must be a 2-d int32 tensor [batch, max_blocks]")
+    for name, t in (("prefix_k", prefix_k), ("prefix_v", prefix_v)):
+        if not isinstance(t, Tensor) or t.dim() != 4 or (not prefix_paged and t.shape[0] != 1):
+            raise ValueError(f"{name} must be a 4-d tensor [1, cap_p, heads_kv, head_dim] (one prefix for the whole batch), or with "
+                             f"prefix_block_table a pool [num_blocks, page_block_size, heads_kv, head_dim]")
+    pool = "num_blocks, page_block_size"
+    batch, seqlen_q, heads_q, head_dim, heads_kv, new = _check_tensors(q, k_cache, v_cache, k, v, pool if paged else "batch, cap")
+    try:  # the prefix is the cache of a batch of one
+        _check_tensors(q[:1], prefix_k, prefix_v, None, None, pool if prefix_paged else "batch, cap")
+        if prefix_k.shape[2] != heads_kv:
+            raise ValueError(f"{prefix_k.shape[2]} kv heads, k_cache has {heads_kv}")
+        cap_p = _check_block_table(prefix_block_table, prefix_k, q[:1]) if prefix_paged else prefix_k.shape[1]
+        prefix_len = _seqlens_on_device(prefix_seqlen, 1, cap_p, q.device)
+    except (ValueError, TypeError, NotImplementedError) as e:
+        raise type(e)(f"prefix_k / prefix_v / prefix_block_table / prefix_seqlen (the k_cache / v_cache / block_table / "
+                      f"cache_seqlens of a batch of 1): {e}") from None
+    cap = _check_block_table(block_table, k_cache, q) if paged else k_cache.shape[1]
+    seqlens = _seqlens_on_device(cache_seqlens, batch, cap, q.device)
+    lib = _lib.load()
+    args = _lib.PrefixKvCacheArgs()
+    base = args.seq.base
+    with torch.no_grad():
+        if seqlen_q > 1 and batch > 1 and q.stride(0) != seqlen_q * q.stride(1):
+            q = q.contiguous()  # the prefix pass reads q as [1, B * Sq, Hq, D]
+        out = torch.empty(q.shape, dtype=q.dtype, device=q.device)
+        lse = torch.empty((batch, heads_q, seqlen_q), dtype=torch.float32, device=q.device) if return_lse else None
+        _fill_cache_side(args.seq, k_cache, v_cache, block_table, seqlens, cap, num_splits)
+        _fill_cache_side(args.prefix, prefix_k, prefix_v, prefix_block_table, prefix_len, cap_p, prefix_num_splits)
+        base.q, base.o = q.data_ptr(), out.data_ptr()
+        base.lse = lse.data_ptr() if return_lse else None
+        base.q_stride[:] = bshd_strides(q)
+        base.o_stride[:] = bshd_strides(out)
+        if new:
+            base.k_new, base.v_new = k.data_ptr(), v.data_ptr()
+            base.k_new_stride[:] = bshd_strides(k)
+            base.v_new_stride[:] = bshd_strides(v)
+            base.seqlen_new = k.shape[1]
+        base.batch, base.heads_q, base.heads_kv = batch, heads_q, heads_kv
+        base.seqlen_q, base.head_dim = seqlen_q, head_dim
+        base.causal = int(bool(causal))
+        base.window_left, base.window_right = left, right
+        base.dtype = encode_dtype(q)
+        base.softmax_scale = 1.0 / math.sqrt(head_dim) if softmax_scale is None else float(softmax_scale)
+        need = lib.fa2_prefix_kvcache_workspace_bytes(ctypes.byref(args))  # a function of the shapes only
+        workspace = None
+        if need > 0:
+            workspace = torch.empty(need, dtype=torch.uint8, device=q.device)
+            base.workspace, base.workspace_bytes = workspace.data_ptr(), need
+        _lib.check(launch_on(q, lambda st: lib.fa2_fwd_kvcache_prefix(ctypes.byref(args), st)))
+    return (out, lse) if return_lse else out
 
 
 def _check_descale(name: str, d) -> None:

@@ -318,6 +318,44 @@ int fa2_fwd_kvcache_fp8(const fa2_fp8_kvcache_args* args, void* stream);
 int fa2_fp8_kvcache_num_splits(const fa2_fp8_kvcache_args* args);
 int64_t fa2_fp8_kvcache_workspace_bytes(const fa2_fp8_kvcache_args* args);
 
+/* Shared-prefix (cascade) decode attention (added within ABI 10 minor 1: detect it by the presence of
+ * the symbol fa2_fwd_kvcache_prefix).  Every query row of `seq` (the call fa2_fwd_kvcache or, with a
+ * block table, fa2_fwd_kvcache_paged would take) attends to the first Lp keys of one prefix cache
+ * that all batch rows share, and to the keys of its own sequence under seq's rule (lengths, append,
+ * causal, window_right); one softmax runs over the union.  Lp is prefix.base.cache_seqlens[0] read
+ * on the device and clamped to [0, prefix.base.capacity] (NULL: the capacity).  A row that sees no
+ * key at all (Lp = 0 and no visible key of its own) gives O = 0 and LSE2 = -inf.
+ *  - the prefix is attended once for the whole batch: the library runs the split kernel of the
+ *    prefix's layout on batch 1 with seqlen_q = B * Sq, no mask and no append, reading q row
+ *    b * Sq + i at q + (b * Sq + i) * row stride.  That needs q_stride[0] == Sq * q_stride[1]; with
+ *    Sq == 1 the batch stride is the row stride and with B == 1 the sequence stride is; anything
+ *    else is FA2_E_UNSUPPORTED.
+ *  - both passes always write fp32 partial results into `seq.base.workspace`, never a rounded O, so
+ *    each runs with at least two key splits: max(2, the automatic count of the pass), or a forced
+ *    2 .. 128 in seq.base.num_splits / prefix.base.num_splits.  A forced 1 is FA2_E_INVALID.  One
+ *    merge kernel sums the prefix splits, then the sequence splits, weighted by their LSE2, and
+ *    rounds O once (bitwise reproducible).
+ *  - workspace: the prefix region [ns_p, 1, Hq, B * Sq, D] fp32 + [ns_p, 1, Hq, B * Sq], then the
+ *    sequence region [ns_s, B, Hq, Sq, D] + [ns_s, B, Hq, Sq], each rounded up to 16 bytes.
+ *  - window_left >= 0 is FA2_E_UNSUPPORTED (the band may or may not reach into the prefix); there is
+ *    no fp8 form.  The layouts of the two sides are independent: a NULL block_table on a side means
+ *    its cache is contiguous ([B, capacity, Hkv, D]; the prefix [1, capacity, Hkv, D]), otherwise
+ *    pools as in fa2_fwd_kvcache_paged (the prefix table is one row), which may be the same pools. */
+typedef struct fa2_prefix_kvcache_args {
+  fa2_paged_kvcache_args seq;     /* the per-sequence call; q, o, lse, k_new / v_new, the masks, the scale and the workspace live here */
+  fa2_paged_kvcache_args prefix;  /* read: k_cache, v_cache, their strides, capacity, cache_seqlens (one int32 or NULL), the paging
+                                     fields and num_splits.  Every other field must be zero */
+} fa2_prefix_kvcache_args;
+
+int fa2_fwd_kvcache_prefix(const fa2_prefix_kvcache_args* args, void* stream);
+/* The key splits of the two passes, into *prefix_splits and *seq_splits (either may be NULL): both
+ * are >= 2 and functions of the shapes only.  Returns FA2_OK, or the status fa2_fwd_kvcache_prefix
+ * would reject the sizes with (both counts are then 0). */
+int fa2_prefix_kvcache_num_splits(const fa2_prefix_kvcache_args* args, int* prefix_splits, int* seq_splits);
+/* Bytes of workspace: round16(ns_p * R) + round16(ns_s * R) with R = B * Hq * Sq * (D + 1) * 4 and
+ * round16 rounding up to a multiple of 16; 0 for sizes the call would reject. */
+int64_t fa2_prefix_kvcache_workspace_bytes(const fa2_prefix_kvcache_args* args);
+
 const char* fa2_last_error(void);
 int fa2_version(void);
 /* Additive revisions of one ABI version (FA2_ABI_VERSION stays what callers compiled against):
